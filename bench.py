@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: quadrature-point stress updates per second.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--n POINTS]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--n POINTS] [--dump-outputs DIR] [--full]
 
 One "step" = one ``evaluate`` pass of one constitutive law over n synthetic quadrature points
 per GPU, device-resident (inputs already in HBM when the timed region starts), committed state in,
@@ -13,23 +13,27 @@ BASELINE.json's target configuration, VonMises3D return mapping, 1e8 points, mix
 few candidate allocations -- the line carries the chosen, the FIRST (what an untuned
 caller gets) and the median candidate.
 
-With no --workload (the driver's command) and N = 1 the same run then times every other single-GPU
-configuration of BASELINE.json / SURVEY.md 8d with the same method -- LinearElasticity (cfg2),
-VonMises3D all-plastic and all-elastic (cfg3 sub-cases), Maxwell (cfg4), Kelvin -- and reports them
-under "configs".  For N > 1 (launched by torch.distributed.run, one rank per GPU) every rank evaluates
-its own contiguous shard of n points (weak scaling, no data-path collective: SURVEY.md 8e); the
-stress/tangent all-gather of the single-assembler mode (config 5) is timed separately on the whole
+A plain run does only what the headline needs: set up, place, warm up, time the K steps, write the
+outputs of the last step (--dump-outputs DIR), print the line.  Everything else the benchmark measures
+runs with --full only, after the timed steps: the same step in the reference's forms and the memory
+floor, the copy probes, the host path, the CPU baseline and the PMC passes; with no --workload and
+N = 1 every other single-GPU configuration of BASELINE.json / SURVEY.md 8d with the same method --
+LinearElasticity (cfg2), VonMises3D all-plastic and all-elastic (cfg3 sub-cases), Maxwell (cfg4),
+Kelvin -- reported under "configs", and the SURVEY 8(f) rows.  For N > 1 (launched by
+torch.distributed.run, one rank per GPU) every rank evaluates its own contiguous shard of n points
+(weak scaling, no data-path collective: SURVEY.md 8e); with --full the strong-scaling leg and the
+stress/tangent all-gather of the single-assembler mode (config 5) are timed separately on the whole
 shard -- stress in one piece, tangent in chunks that fit next to the working set -- and reported under
-"allgather", never inside `value`.
+"strong_scaling" / "allgather", never inside `value`.
 
 Rank 0 prints ONE compact JSON line (< 4 KB, numbers only: benchlib/line.py; see DESIGN.md "Measurement") and writes the full
 record -- workload sentences, launch logs, placement candidates, host-path tables, notes -- to the detail file the line names
 (--detail, default gpurun_out/bench_detail.json).  `roofline.traffic` (HBM bytes per launch by the PMC counters) is measured at the
-end of an N = 1 run by two child passes of this file under `rocprofv3 --pmc` (one pass per counter; every measured workload runs in
-the same child: --pmc-child) while the CPU baseline runs on the host (--no-live-traffic: the stored figure of profiles/traffic.json
-instead).  The default command is the lean one (about two minutes); --full adds the per-configuration CPU figures, the small-call
-crossover table, more allocation draws per row and PMC passes for every configuration.  `--plan` prints what a run with these
-arguments WOULD do -- per-leg memory and time estimates, no GPU work.
+end of an N = 1 --full run by two child passes of this file under `rocprofv3 --pmc` (one pass per counter; every measured workload
+runs in the same child: --pmc-child) after the CPU baseline (--no-live-traffic: the stored figure of profiles/traffic.json
+instead; a plain run always reports the stored figure).  --full takes about three minutes: it also carries the per-configuration CPU
+figures, the small-call crossover table, three allocation draws per 8(f) row and PMC passes for every configuration.  `--plan`
+prints what a run with these arguments WOULD do -- per-leg memory and time estimates, no GPU work.
 """
 
 from __future__ import annotations
@@ -177,6 +181,55 @@ def all_agree(flag, dist, device):
     return bool(int(f.item()))
 
 
+DUMP_POINTS = 65536  # points of the --dump-outputs sample: 49-55 doubles each (stress, tangent, history), under 30 MB in all
+DUMP_SEED = 20261015
+
+
+def dump_sample(n, points=DUMP_POINTS):
+    """the point indices of the --dump-outputs sample: every point up to `points`, else a fixed seeded draw (ascending)"""
+    import numpy as np
+
+    if n <= points:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=points, replace=False)).astype(np.int64)
+
+
+def packed_rows_at(packed, ever, ix):
+    """rows `ix` of a packed plastic-strain array (FCAMD_EVAL_PACKED_HISTORY) in the reference's layout: what
+    fenics_constitutive_amd.device.unpack_rows(packed, ever)[ix] gives, without unpacking the whole array"""
+    import torch
+
+    tile, bit = ix // 64, ix % 64
+    shifts = torch.arange(64, device=ix.device, dtype=torch.int64)
+    bits = (ever[tile][:, None] >> shifts[None, :]) & 1
+    rank = (bits * (shifts[None, :] < bit[:, None])).sum(dim=1)  # ever-plastic points before this one in its tile
+    rows = packed.view(-1, 6)[tile * 64 + rank]
+    return torch.where(bits.gather(1, bit[:, None]).bool(), rows, torch.zeros_like(rows))
+
+
+def dump_outputs(wl, out_dir):
+    """--dump-outputs DIR: what the timed path computed in its last step -- the trial stress, tangent and trial history a caller
+    of the resident evaluate receives (history in the reference's layout) -- at the points of dump_sample(n), as float64
+    DIR/points.npy [k] (the indices), stress.npy [k, 6], tangent.npy [k, 36], history_<key>.npy [k, dim]"""
+    import numpy as np
+
+    torch = wl.torch
+    n = wl.n
+    idx = dump_sample(n)
+    ix = torch.from_numpy(idx).to(wl.device)
+    out = {"points": idx.astype(np.float64), "stress": wl.stress_t.view(n, 6)[ix], "tangent": wl.tangent.view(n, 36)[ix]}
+    hist = {}
+    for key, v in (wl.hist_t or {}).items():
+        hist[key] = packed_rows_at(v, wl.ever_t, ix) if (wl.packed and key == wl.rows_key) else v.view(n, -1)[ix]
+    if wl.split:  # the reference's 7-double rows: [scalar, plastic strain]
+        hist = {"history": torch.cat([hist["scalar"], hist["rows"]], dim=1)}
+    out.update({f"history_{k}": v for k, v in hist.items()})
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        a = a.cpu().numpy() if torch.is_tensor(a) else a
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main_frow(args):
     """`--frow NAME`: one SURVEY 8(f) row alone; prints one JSON line (with the launch_log the PMC slicing needs)"""
     import torch
@@ -274,12 +327,17 @@ def main():
     ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
                     help="where the full record behind the compact stdout line is written (the line carries the path)")
     ap.add_argument("--full", action="store_true",
-                    help="everything round 4's default ran: per-configuration CPU figures, small-call crossover table, three allocation draws per 8(f) row, "
-                         "four placement candidates per configuration, PMC passes for the configurations too (about four minutes)")
+                    help="after the timed steps, everything besides the headline: the reference's forms of the step and its memory floor, copy probes, "
+                         "the other configurations and 8(f) rows (--configs auto), host path, CPU baseline (per configuration too, small-call crossover "
+                         "table), PMC passes, at N > 1 the strong-scaling, all-gather and host_path_multi legs; three allocation draws per 8(f) row, "
+                         "four placement candidates per configuration (about three minutes).  Without it a run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (trial stress, tangent, trial history) at a fixed, seeded "
+                         f"sample of {DUMP_POINTS} points (all points below that) as DIR/<name>.npy, float64; rank 0's shard at N > 1")
     ap.add_argument("--plan", action="store_true", help="print the legs, memory and time estimates of a run with these arguments; no GPU work")
-    ap.add_argument("--no-frows", action="store_true", help="N = 1 default run: skip the SURVEY 8(f) rows after the BASELINE configurations")
+    ap.add_argument("--no-frows", action="store_true", help="N = 1 --full run: skip the SURVEY 8(f) rows after the BASELINE configurations")
     ap.add_argument("--configs", choices=["auto", "all", "none"], default="auto",
-                    help="the other single-GPU BASELINE configurations after the headline: auto = when no --workload is given and N = 1")
+                    help="the other single-GPU BASELINE configurations after the headline: auto = with --full, when no --workload is given and N = 1")
     ap.add_argument("--config-steps", type=int, default=6, help="timed launches per extra configuration (>= 5)")
     ap.add_argument("--n", "--points", dest="n", type=int, default=None,
                     help="quadrature points per GPU (use --points under torch.distributed.run, whose parser claims --n); default 1e8, "
@@ -331,7 +389,7 @@ def main():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="N > 1: weak = --points per GPU (default; a strong-scaling leg on the first points/N of every shard is reported "
                          "next to it under \"strong_scaling\"); strong = --points in total, cut into N contiguous shards")
-    ap.add_argument("--no-host-path", action="store_true", help="N = 1 default run: skip the host_path block (PCIe-inclusive figures of the ndarray entries)")
+    ap.add_argument("--no-host-path", action="store_true", help="N = 1 --full run: skip the host_path block (PCIe-inclusive figures of the ndarray entries)")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="N = 1: do not measure roofline.traffic in this run (two child passes under rocprofv3 --pmc, about 40 s); the "
                          "stored figure of profiles/traffic.json is reported instead (labelled as stored)")
@@ -339,6 +397,8 @@ def main():
                     help="seconds of wall clock after which the optional legs (strong-scaling leg, gather variants, extra configurations, host_path) "
                          "are skipped so that the line is printed inside the driver's limit")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode == "host":
+        ap.error("--dump-outputs: device mode only")
     if args.n is None:
         args.n = 10_000_000 if args.mode == "host" else 100_000_000
     if args.mode == "host":
@@ -456,11 +516,14 @@ def main():
         tk[rank] = kernel_avg_ms
         dist.all_reduce(tk, op=dist.ReduceOp.SUM)
         per_rank_ms = [round(float(x), 4) for x in tk.tolist()]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, args.dump_outputs)
+        stage(f"outputs of the last step written to {args.dump_outputs}")
 
     # N > 1, weak run: the strong-scaling figure next to it -- the same total as ONE GPU's shard (--points), i.e. every rank
     # evaluates the first points/world points (tile-aligned) of its arrays; same bracket (barrier + synchronize, max over ranks)
     strong = None
-    if distributed and world > 1 and args.scaling == "weak" and agree(budget_left() > 60):
+    if args.full and distributed and world > 1 and args.scaling == "weak" and agree(budget_left() > 60):
         m = max(64, (args.n // world // 64) * 64)
         for i in range(max(2, args.warmup)):
             wl.launch(i, m=m)
@@ -501,13 +564,13 @@ def main():
     # next to the headline: the same step without the sparse protocol (every launch rewrites the whole trial
     # history, fcamd_evaluate_device_from) -- six extra launches after the timed region
     full_ms = None
-    if wl.sparse:
+    if args.full and wl.sparse:
         ms = wl.timed_events(6, phase="full_trial_history", full_history=True, sparse_tangent=False)
         full_ms = sum(ms[1:]) / (len(ms) - 1)
 
     # ... the sparse protocol on the reference's array layout (ResidentState(packed_history=False); the headline of rounds 1-3)
     unpacked_ms = None
-    if wl.packed:
+    if args.full and wl.packed:
         wl.launch(0, unpacked=True), wl.launch(1, unpacked=True)
         wl.launch_log.append(["sparse_unpacked_history_warm", 2])
         ms = wl.timed_events(6, phase="sparse_unpacked_history", unpacked=True, sparse_tangent=False)
@@ -516,7 +579,7 @@ def main():
     # ... and the reference's own call: law.evaluate(...) IN PLACE on the interface's arrays (what a drop-in torch caller launches;
     # the committed state is copied into the call's arrays before every launch, outside the event bracket)
     in_place_ms = in_place_draws = None
-    if wl.plasticity and not wl.split and world == 1:
+    if args.full and wl.plasticity and not wl.split and world == 1:
         try:
             ms = wl.timed_in_place(5, sets=2)
             in_place_ms = sum(ms) / len(ms)
@@ -525,62 +588,64 @@ def main():
             stage(f"in-place leg skipped: {type(e).__name__}: {e}")
     # ... and what the memory system alone takes for the headline's request stream: the kernel's synthetic twin
     mem_floor_ms = in_place_lines = None
-    if world == 1:
+    if args.full and world == 1:
         try:
             mem_floor_ms = wl.mem_floor(4)
             if in_place_ms is not None:
                 in_place_lines = wl.in_place_line_bytes()
         except Exception as e:  # informational
             stage(f"mem-floor leg skipped: {type(e).__name__}: {e}")
-    leg_done("reference_layout_legs")
+    if args.full:
+        leg_done("reference_layout_legs")
 
     # "achievable" next to "peak" (SURVEY 8d): a plain device copy over half of the tangent array
     # (read + write counted)
     copy_gbs = stream_copy_gbs = fill_gbs = read_gbs = None
-    try:
-        half = (wl.tangent.numel() // 2) & ~1
-        cs, ce = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        best = None
-        for _ in range(4):
-            cs.record()
-            wl.tangent[:half].copy_(wl.tangent[half : 2 * half])
-            ce.record()
-            ce.synchronize()
-            ms_ = cs.elapsed_time(ce)
-            best = ms_ if best is None else min(best, ms_)
-        copy_gbs = 2 * 8 * half / (best * 1e-3) / 1e9
-        # ... and the library's own copy kernel (fcamd_copy_device: the evaluate kernels' access pattern -- 16 B per lane,
-        # non-temporal -- with nothing but the copy): what this box's memory gives a kernel of this kind
-        from fenics_constitutive_amd.hostio import copy_device
-
-        best = None
-        for _ in range(5):
-            cs.record()
-            copy_device(wl.tangent[:half], wl.tangent[half : 2 * half])
-            ce.record()
-            ce.synchronize()
-            ms_ = cs.elapsed_time(ce)
-            best = ms_ if best is None else min(best, ms_)
-        stream_copy_gbs = 2 * 8 * half / (best * 1e-3) / 1e9
-        # ... and the two directions on their own: a pure write (fill) and a pure read (sum) of the same memory
-        rates = {}
-        for key, fn in (("fill", lambda: wl.tangent[:half].fill_(1.0)), ("read", lambda: wl.tangent[half : 2 * half].sum())):
-            fn()
+    if args.full:
+        try:
+            half = (wl.tangent.numel() // 2) & ~1
+            cs, ce = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             best = None
             for _ in range(4):
                 cs.record()
-                fn()
+                wl.tangent[:half].copy_(wl.tangent[half : 2 * half])
                 ce.record()
                 ce.synchronize()
                 ms_ = cs.elapsed_time(ce)
                 best = ms_ if best is None else min(best, ms_)
-            rates[key] = 8 * half / (best * 1e-3) / 1e9
-        fill_gbs, read_gbs = rates["fill"], rates["read"]
-    except Exception:  # the probe is informational only
-        copy_gbs = None
+            copy_gbs = 2 * 8 * half / (best * 1e-3) / 1e9
+            # ... and the library's own copy kernel (fcamd_copy_device: the evaluate kernels' access pattern -- 16 B per lane,
+            # non-temporal -- with nothing but the copy): what this box's memory gives a kernel of this kind
+            from fenics_constitutive_amd.hostio import copy_device
+
+            best = None
+            for _ in range(5):
+                cs.record()
+                copy_device(wl.tangent[:half], wl.tangent[half : 2 * half])
+                ce.record()
+                ce.synchronize()
+                ms_ = cs.elapsed_time(ce)
+                best = ms_ if best is None else min(best, ms_)
+            stream_copy_gbs = 2 * 8 * half / (best * 1e-3) / 1e9
+            # ... and the two directions on their own: a pure write (fill) and a pure read (sum) of the same memory
+            rates = {}
+            for key, fn in (("fill", lambda: wl.tangent[:half].fill_(1.0)), ("read", lambda: wl.tangent[half : 2 * half].sum())):
+                fn()
+                best = None
+                for _ in range(4):
+                    cs.record()
+                    fn()
+                    ce.record()
+                    ce.synchronize()
+                    ms_ = cs.elapsed_time(ce)
+                    best = ms_ if best is None else min(best, ms_)
+                rates[key] = 8 * half / (best * 1e-3) / 1e9
+            fill_gbs, read_gbs = rates["fill"], rates["read"]
+        except Exception:  # the probe is informational only
+            copy_gbs = None
 
     cpu_args = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # sample of the headline arrays, taken before they are released for the other configurations
         from benchlib.cpu import host_sample
 
@@ -704,7 +769,7 @@ def main():
                 os.kill(os.getpid(), 9)
 
     # the exchange step of config 5, timed separately (never part of `value`)
-    do_gather = distributed and world > 1 and not args.no_gather
+    do_gather = args.full and distributed and world > 1 and not args.no_gather
     if do_gather and not agree(budget_left() > 90):
         do_gather = False
         if rank == 0:
@@ -743,7 +808,7 @@ def main():
     if distributed and world > 1:
         leg_done("multi_gpu_legs")
     # every other single-GPU configuration of BASELINE.json, same method, >= 5 event-timed launches each
-    do_configs = args.configs == "all" or (args.configs == "auto" and args.workload is None and world == 1)
+    do_configs = args.configs == "all" or (args.configs == "auto" and args.full and args.workload is None and world == 1)
     if do_configs and rank == 0:
         configs = {}
         for k, cname in enumerate(EXTRA_CONFIGS):
@@ -794,7 +859,7 @@ def main():
     # N > 1: the single-process form of the host path on THIS node's GPUs (fcamd_multi) -- rank 0 alone drives all
     # of them over their own PCIe links while the other ranks wait on the CPU (a key in the process group's store, not a
     # collective: an RCCL barrier would keep their GPUs busy with a spinning kernel)
-    if distributed and world > 1 and not args.no_host_path:
+    if args.full and distributed and world > 1 and not args.no_host_path:
         import datetime
 
         store = None
@@ -837,7 +902,7 @@ def main():
                 pass  # rank 0 is late or gone: the closing barrier below decides
 
     if rank == 0:
-        if world == 1 and not args.no_host_path and args.workload is None and budget_left() > 40:
+        if args.full and world == 1 and not args.no_host_path and args.workload is None and budget_left() > 40:
             # the number a dolfinx user sees: the ndarray entries over PCIe ("timed separately and labelled as such")
             checkpoint("host_path")
             try:
@@ -851,7 +916,7 @@ def main():
         # two rocprofv3 children starting Python and parsing CSVs on the same cores can only slow the figure the GPU is compared with,
         # and the all-cores leg, 256 threads under a cgroup quota of 16 CPUs, came out at the one-thread rate: ADVICE r5)
         cpu_thread = None
-        if world == 1:
+        if args.full and world == 1:
             checkpoint("cpu_baseline")
             if cpu_args is not None:
                 try:
@@ -861,7 +926,7 @@ def main():
                 leg_done("cpu_baseline")
             else:
                 out["cpu_baseline"] = None
-        if world == 1 and not args.no_live_traffic and budget_left() > 100:
+        if args.full and world == 1 and not args.no_live_traffic and budget_left() > 100:
             # roofline.traffic measured in THIS run (the kernels' memory is free by now); the stored figure stays next to it
             checkpoint("live_traffic")
             extra = (["--no-split-history"] if args.no_split_history else []) \

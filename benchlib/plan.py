@@ -43,13 +43,15 @@ def bench_plan(args):
                      f"{tries} hipMalloc candidates of the tangent (4 launches each) + one interleaved VMM working set"))
     legs.append(_leg("timed_steps", (warmup + 2 + steps) * step_s + 0.5, state_gb, f"{warmup} warm-up + 2 counting + {steps} timed launches, barrier + synchronize brackets"))
     total_pts = n * world
-    if world > 1:
+    full = bool(args.full)  # everything after the timed steps runs with --full only
+    if full and world > 1:
         m = max(64, (n // world // 64) * 64)
         legs.append(_leg("strong_scaling_leg", (max(2, warmup) + steps + 2) * (m * ALG_B / (KERNEL_GBS * 1e9)) + 0.5, state_gb,
                          f"the first {m} points of every shard ({m * world} in total): same bracket"))
-    legs.append(_leg("reference_layout_legs", 3.0 + 19 * step_s + ALLOC_S_PER_GB * 0.2 * state_gb, state_gb * 1.2,
-                     "full trial history, sparse protocol on the reference layout" + ("" if world > 1 else ", in-place call")))
-    if world > 1 and not args.no_gather:
+    if full:
+        legs.append(_leg("reference_layout_legs", 3.0 + 19 * step_s + ALLOC_S_PER_GB * 0.2 * state_gb, state_gb * 1.2,
+                         "full trial history, sparse protocol on the reference layout" + ("" if world > 1 else ", in-place call")))
+    if full and world > 1 and not args.no_gather:
         ng = ((min(args.gather_points, n) if args.gather_points > 0 else n) // 64) * 64
         shard_gb = 336 * ng / 1e9
         stress_all_gb = 48 * ng * world / 1e9
@@ -64,14 +66,15 @@ def bench_plan(args):
         legs.append(_leg("allgather", t, HBM_GB - 8.0,
                          f"shard {shard_gb:.1f} GB/GPU, stress gathered whole ({stress_all_gb:.1f} GB), tangent in ~{chunks} chunks through two buffers "
                          f"({buf_gb:.0f} GB); link-rate bounds: direct {direct_s:.2f} s, ring {ring_s:.2f} s; watchdog --gather-timeout {args.gather_timeout:.0f} s"))
-    if world == 1 and args.workload is None and args.configs != "none":
+    do_configs = args.configs == "all" or (args.configs == "auto" and full)
+    if world == 1 and args.workload is None and do_configs:
         cfg_tries = 4 if args.full else 3
         legs.append(_leg("configs", 5 * (ALLOC_S_PER_GB * (state_gb + (cfg_tries - 1) * tan_gb) + 3.0 + (4 * cfg_tries + 12) * step_s * 1.2), state_gb + (cfg_tries - 1) * tan_gb,
                          f"five other BASELINE configurations, {cfg_tries} tangent candidates each"))
         if not args.no_frows:
             draws = 3 if args.full else 2
             legs.append(_leg("frows", 10 * draws * (ALLOC_S_PER_GB * 0.7 * state_gb + 1.2), draws * 0.8 * state_gb, f"ten SURVEY 8(f) rows, up to {draws} sets of allocations each"))
-    if not args.no_host_path:
+    if full and not args.no_host_path:
         if world > 1:
             per_dev = min(n, 2_500_000)
             pts = per_dev * world
@@ -80,9 +83,9 @@ def bench_plan(args):
         elif args.workload is None:
             big = min(n, 10_000_000 if args.full else 4_000_000)
             legs.append(_leg("host_path", 2.0 + big * 568 / 2.0e9 + 18 * big * 400 / (PCIE_GBS * 1e9), 1.0, f"ndarray entries over PCIe at 1e6 and {big} points"))
-    if world == 1:
+    if full and world == 1:
         if not args.no_live_traffic:
-            extra_rows = args.workload is None and args.configs != "none"
+            extra_rows = args.workload is None and do_configs
             items = 3 + (5 if extra_rows else 0) + (10 if (extra_rows and not args.no_frows) else 0)
             legs.append(_leg("live_traffic", 2 * (IMPORT_S + 4.0 + items * (ALLOC_S_PER_GB * 0.8 * state_gb + 1.5)), state_gb,
                              f"two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE), {items} items each; the CPU baseline (~20 s, alone on the host) runs before them"))
@@ -103,5 +106,5 @@ def bench_plan(args):
             "wall_budget_s": args.wall_budget, "driver_limit_s": DRIVER_LIMIT_S, "fits_driver_limit": total < 0.8 * DRIVER_LIMIT_S,
             "peak_GB_per_gpu": peak, "fits_memory": peak <= HBM_GB, "est_value_Mpts_s": round(total_pts / step_s / 1e6, 0),
             "legs": legs,
-            "note": "estimates from single-GPU measurements of this round and the guide's link rates; legs after `timed_steps` are optional: each is skipped "
-                    "when --wall-budget runs low (all ranks agree by all-reduce), and the line printed before it survives a leg that dies"}
+            "note": "estimates from single-GPU measurements of this round and the guide's link rates; legs after `timed_steps` run with --full only and "
+                    "are optional: each is skipped when --wall-budget runs low (all ranks agree by all-reduce), and the line printed before it survives a leg that dies"}

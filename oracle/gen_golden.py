@@ -571,8 +571,40 @@ def main_mises_limit():
     print("drucker_prager_volumetric_flow.npz", idx, "calls")
 
 
+def main_interface():
+    """The reference's model interface as data (tests/test_host_logic.py: drop-in mode): the members of StressStrainConstraint
+    with their dimensions, the abstract and property members of IncrSmallStrainModel, the parameters of `evaluate`, and what two
+    reference laws report through the interface.  Lets the drop-in test build a stand-in of the interface module without the
+    reference on the machine."""
+    import inspect
+
+    m = import_reference()
+    C, M = m.StressStrainConstraint, m.IncrSmallStrainModel
+    members = list(C)
+    props = sorted(k for k, v in vars(M).items() if isinstance(v, property))
+    vm = m.VonMises3D(dict(p_ka=1.0, p_mu=1.0, p_y0=1.0, p_y00=2.0, p_w=1.0))
+    le = m.LinearElasticityModel({"E": 42.0, "nu": 0.3}, C.PLANE_STRESS)
+    d = {
+        "constraint_names": np.array([c.name for c in members]),
+        "constraint_values": np.array([c.value for c in members], dtype=np.int64),
+        "constraint_stress_strain_dim": np.array([c.stress_strain_dim for c in members], dtype=np.int64),
+        "constraint_geometric_dim": np.array([c.geometric_dim for c in members], dtype=np.int64),
+        "abstract_members": np.array(sorted(M.__abstractmethods__)),
+        "property_members": np.array(props),
+        "evaluate_parameters": np.array(list(inspect.signature(M.evaluate).parameters)),
+        "von_mises_3d_history_keys": np.array(list(vm.history_dim)),
+        "von_mises_3d_history_dims": np.array(list(vm.history_dim.values()), dtype=np.int64),
+        "linear_elasticity_plane_stress_dims": np.array([le.stress_strain_dim, le.geometric_dim], dtype=np.int64),
+    }
+    os.makedirs(OUT, exist_ok=True)
+    np.savez_compressed(os.path.join(OUT, "reference_interface.npz"), **d)
+    print("reference_interface.npz", len(members), "constraints,", len(d["abstract_members"]), "abstract members")
+
+
 if __name__ == "__main__":
-    if "--mises-limit" in sys.argv:
+    if "--interface" in sys.argv:
+        main_interface()
+    elif "--mises-limit" in sys.argv:
         main_mises_limit()
     elif "--random-parameters" in sys.argv:
         main_random_parameters()
@@ -589,3 +621,4 @@ if __name__ == "__main__":
         main_material_point()
         main_random_parameters()
         main_mises_limit()
+        main_interface()

@@ -79,8 +79,8 @@ def run_plan(*args):
 
 def test_plan_of_the_eight_gpu_launch_fits_the_limits():
     """the driver's N = 8 command (config 5: 8 x 1e8 points): no GPU work, and by the plan's own arithmetic the run fits 288 GB per
-    GPU and -- with margin -- the driver's 600 s, the gather leg inside its watchdog"""
-    p = run_plan("--gpus", "8")
+    GPU and -- with margin -- the driver's 600 s, the gather leg inside its watchdog (--full: the legs after the timed steps)"""
+    p = run_plan("--gpus", "8", "--full")
     assert p["n_gpus"] == 8 and p["points_total"] == 800_000_000
     assert p["fits_memory"] and p["peak_GB_per_gpu"] <= 288.0
     assert p["fits_driver_limit"] and p["est_total_s"] < 0.5 * p["driver_limit_s"] and p["est_total_s"] < p["wall_budget_s"]
@@ -97,13 +97,45 @@ def test_plan_of_the_eight_gpu_launch_fits_the_limits():
 
 
 def test_plan_of_the_default_command_is_under_two_minutes_plus_margin():
-    p = run_plan()
+    p = run_plan("--full")
     assert p["n_gpus"] == 1 and p["fits_memory"] and p["est_total_s"] < 180.0
     legs = {x["leg"] for x in p["legs"]}
     assert {"configs", "frows", "host_path", "live_traffic", "cpu_baseline"} <= legs
     for n in ("2", "4"):
-        q = run_plan("--gpus", n)
+        q = run_plan("--gpus", n, "--full")
         assert q["fits_memory"] and q["fits_driver_limit"]
+
+
+def test_plan_of_a_plain_run_is_the_headline_alone():
+    """without --full a run sets up, places, warms up and times its steps, nothing after them -- at every N"""
+    for args in ((), ("--gpus", "8"), ("--steps", "50", "--warmup", "5")):
+        p = run_plan(*args)
+        assert [x["leg"] for x in p["legs"]] == ["setup", "placement", "timed_steps"], (args, p["legs"])
+        assert p["fits_memory"] and p["est_total_s"] < 30.0, (args, p["est_total_s"])
+
+
+def test_dump_sample_is_fixed_and_packed_rows_are_read_in_the_reference_layout():
+    """--dump-outputs: the same points for the same n in every run (all of them for small n), and the trial plastic strain of a
+    packed state read at those points equals the unpacked array there (full tiles included: bit 63 is the sign bit)"""
+    import numpy as np
+    import torch
+
+    import bench
+    from fenics_constitutive_amd.device import pack_rows, unpack_rows
+
+    big = bench.dump_sample(100_000_000)
+    assert big.size == bench.DUMP_POINTS and np.array_equal(big, bench.dump_sample(100_000_000))
+    assert np.all(np.diff(big) > 0) and big[0] >= 0 and big[-1] < 100_000_000
+    assert np.array_equal(bench.dump_sample(1000), np.arange(1000))
+    g = torch.Generator().manual_seed(0)
+    for n in (1, 63, 64, 65, 1000, 70_001):
+        rows = torch.randn(n, 6, generator=g, dtype=torch.float64)
+        rows[torch.rand(n, generator=g) < 0.6] = 0.0
+        rows[64:128] = 1.0
+        packed, ever = pack_rows(rows.reshape(-1))
+        ix = torch.from_numpy(bench.dump_sample(n, points=min(n, 5000)))
+        assert torch.equal(bench.packed_rows_at(packed, ever, ix), unpack_rows(packed, ever, n).view(n, 6)[ix]), n
+        assert torch.equal(bench.packed_rows_at(packed, ever, ix), rows[ix]), n
 
 
 def test_round5_line_is_what_compact_line_makes_of_its_detail_file():

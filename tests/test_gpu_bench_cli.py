@@ -68,7 +68,7 @@ def run_bench(*args, timeout=420, env=None, live_traffic=False):
 
 def test_two_ranks_weak_scaling_with_strong_leg_and_gather():
     r, out = run_bench("--gpus", "2", "--backend", "gloo", "--points", "2000000", "--steps", "3", "--warmup", "2",
-                       "--configs", "none", "--no-cpu-baseline", "--placement-tries", "2")
+                       "--configs", "none", "--no-cpu-baseline", "--placement-tries", "2", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     assert out is not None, r.stdout[-2000:]
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["scaling"] == "weak" and out["unit"] == "Mpts/s"
@@ -96,7 +96,7 @@ def test_four_ranks_rehearsal():
     tests/test_sharded_gloo.py): staggered peer order, three peers per rank in the IPC gather, a chunk plan forced down to
     several chunks, four device contexts in the host_path_multi leg."""
     r, out = run_bench("--gpus", "4", "--backend", "gloo", "--points", "1000000", "--steps", "2", "--warmup", "1", "--configs", "none",
-                       "--no-cpu-baseline", "--placement", "first", "--gather-points", "300000")
+                       "--no-cpu-baseline", "--placement", "first", "--gather-points", "300000", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     assert out["n_gpus"] == 4 and len(out["per_rank_kernel_ms"]) == 4 and out["config"]["points_total"] == 4_000_000
     assert out["strong_scaling"]["points_per_gpu"] == (1_000_000 // 4 // 64) * 64 and len(out["strong_scaling"]["per_rank_kernel_ms"]) == 4
@@ -128,7 +128,7 @@ def test_a_hung_gather_leg_is_a_failed_run():
     """--gather-timeout fires (here at once): rank 0 still prints the line -- with the step timing and an error entry for the
     leg -- and the processes end with a NON-ZERO exit code (a hung exchange used to be reported as rc 0)."""
     r, out = run_bench("--gpus", "2", "--backend", "gloo", "--points", "4000000", "--steps", "2", "--warmup", "1", "--configs", "none",
-                       "--no-cpu-baseline", "--placement", "first", "--gather-timeout", "0.0", "--wall-budget", "1000")
+                       "--no-cpu-baseline", "--placement", "first", "--gather-timeout", "0.0", "--wall-budget", "1000", "--full")
     assert r.returncode != 0
     assert out is not None and out["n_gpus"] == 2 and out["value"] > 0
     assert "did not finish" in out["allgather"]["error"]
@@ -140,7 +140,7 @@ def test_the_line_survives_the_death_of_rank0_in_an_optional_leg(leg, gpus):
     marked incomplete, and the job fails"""
     extra = ["--backend", "gloo"] if gpus > 1 else []
     r, out = run_bench("--gpus", str(gpus), *extra, "--points", "1000000", "--steps", "2", "--warmup", "1", "--configs", "none",
-                       "--no-cpu-baseline", "--placement", "first", env={"BENCH_DIE_IN": leg}, live_traffic=leg == "live_traffic")
+                       "--no-cpu-baseline", "--placement", "first", "--full", env={"BENCH_DIE_IN": leg}, live_traffic=leg == "live_traffic")
     assert r.returncode != 0
     assert out is not None and out["n_gpus"] == gpus and out["value"] > 0 and out["roofline"]["frac"] > 0
     assert leg in out["incomplete"] and leg not in out
@@ -161,8 +161,8 @@ def test_host_mode_two_contexts():
 
 
 def test_default_line_carries_the_host_path_block():
-    """the driver's command shape at a small size: one rank, no launcher, extra configurations off"""
-    r, out = run_bench("--points", "2000000", "--steps", "3", "--warmup", "1", "--configs", "none", "--no-cpu-baseline", live_traffic=True)
+    """the --full command shape at a small size: one rank, no launcher, extra configurations off"""
+    r, out = run_bench("--points", "2000000", "--steps", "3", "--warmup", "1", "--configs", "none", "--no-cpu-baseline", "--full", live_traffic=True)
     assert r.returncode == 0, r.stderr[-2000:]
     assert out["n_gpus"] == 1 and out["scaling"] == "weak"
     import shutil
@@ -204,13 +204,13 @@ def test_one_rank_under_the_launcher_with_rccl(tmp_path):
 
 
 def test_default_legs_at_small_size_carry_every_configuration_and_8f_row():
-    """The driver's command shape (N = 1, no --workload) at 2e6 points: the line carries the five other BASELINE configurations
+    """The --full command shape (N = 1, no --workload) at 2e6 points: the line carries the five other BASELINE configurations
     and every SURVEY 8(f) row, each with a kernel time, a roofline fraction and a launch log whose phases end with the timed one (and, for the rows that have one,
     the measurement of their synthetic twin: mem_floor_ms)."""
     from benchlib import frows
 
     r, out = run_bench("--points", "2000000", "--steps", "3", "--warmup", "1", "--config-steps", "5", "--no-cpu-baseline", "--no-host-path",
-                       "--placement-tries", "2")
+                       "--placement-tries", "2", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     assert out["n_gpus"] == 1 and out["value"] > 0 and 0 < out["roofline"]["frac"] < 1
     cfg = out["configs"]
@@ -230,3 +230,40 @@ def test_default_legs_at_small_size_carry_every_configuration_and_8f_row():
     assert LAST_LINE["configs_columns"] == CONFIG_COLUMNS and set(LAST_LINE["configs"]) == set(cfg)
     for name, row in LAST_LINE["configs"].items():
         assert row[0] == cfg[name]["frac"] and row[2] == cfg[name]["kernel_ms_avg"], (name, row)
+
+
+def test_a_plain_run_times_the_headline_alone_and_dumps_the_same_outputs_every_time(tmp_path):
+    """Without --full: setup, placement, warm-up, exactly --steps timed launches and nothing after them; --dump-outputs writes the
+    last step's trial stress, tangent and trial history (reference layout) at the same sampled points, bit for bit the same in two
+    runs with the same arguments (the inputs are seeded)"""
+    import numpy as np
+
+    import bench
+
+    n, steps, dumps = 2_000_000, 7, []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        r, out = run_bench("--points", str(n), "--steps", str(steps), "--warmup", "2", "--placement-tries", "2", "--dump-outputs", str(d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert out["steps"] == steps and out["n_gpus"] == 1 and out["dtype"] == "f64" and out["unit"] == "Mpts/s" and out["higher_is_better"]
+        assert abs(out["value"] - n * steps / (out["ms_per_step"] * steps * 1e-3) / 1e6) <= 0.01 * out["value"]
+        phases = [ph for ph, _ in out["launch_log"]]
+        assert phases[-1] == "timed" and out["launch_log"][-1][1] == steps, out["launch_log"]
+        assert set(out["legs_s"]) == {"import_and_setup", "headline"}, out["legs_s"]
+        for key in ("configs", "cpu_baseline", "host_path", "full_trial_history", "sparse_unpacked_history", "in_place", "strong_scaling", "allgather"):
+            assert key not in out, key
+        assert "mem_floor_ms" not in out["roofline"] and out["roofline"]["device_copy_GBs"] is None
+        for key in ("configs", "cpu_baseline", "host_path_Mpts_s", "incomplete"):
+            assert key not in LAST_LINE, key
+        files = {f.name: np.load(f) for f in sorted(d.iterdir())}
+        assert set(files) == {"points.npy", "stress.npy", "tangent.npy", "history_eps_n.npy", "history_alpha.npy"}, sorted(files)
+        k_pts = bench.DUMP_POINTS
+        assert np.array_equal(files["points.npy"], bench.dump_sample(n).astype(np.float64))
+        shapes = {"points.npy": (k_pts,), "stress.npy": (k_pts, 6), "tangent.npy": (k_pts, 36), "history_eps_n.npy": (k_pts, 6), "history_alpha.npy": (k_pts, 1)}
+        for name, a in files.items():
+            assert a.dtype == np.float64 and a.shape == shapes[name] and np.all(np.isfinite(a)), name
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+        assert np.count_nonzero(files["history_eps_n.npy"].any(axis=1)) > 0 and np.count_nonzero(files["tangent.npy"]) > 0
+        dumps.append(files)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name

@@ -283,41 +283,63 @@ def test_header_constants_match_the_ctypes_module():
     assert _capi.COUNTER_WORDS == 4 * defines["FCAMD_COUNTER_SLOTS"]  # FCAMD_COUNTER_WORDS is an expression in the header
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="reference checkout not present")
 def test_drop_in_mode_subclasses_the_reference_interface():
-    """With the reference importable (here: its NumPy part, dolfinx / the compiled bindings stubbed as
-    in SURVEY Appendix A) the GPU-backed laws are subclasses of the REFERENCE ABC and carry the
-    REFERENCE enum, which is what IncrSmallStrainProblem checks (solver/_solver.py:67-75)."""
+    """With the reference's interface module importable (``fenics_constitutive.models.interfaces``) the GPU-backed laws are
+    subclasses of the REFERENCE ABC and carry the REFERENCE enum, which is what IncrSmallStrainProblem checks
+    (solver/_solver.py:67-75).  The module is a stand-in built from tests/golden/reference_interface.npz (oracle/gen_golden.py
+    --interface: the reference's enum members and dimensions, the ABC's abstract and property members, the parameters of
+    ``evaluate``, what its VonMises3D / LinearElasticityModel report): instantiating a law proves it implements every abstract
+    member the reference declares."""
     import subprocess
     import sys
     import textwrap
 
     code = textwrap.dedent(
         """
-        import sys, types
-        df = types.ModuleType("dolfinx"); common = types.ModuleType("dolfinx.common")
-        common.timed = lambda name: (lambda f: f); df.common = common
-        sys.modules["dolfinx"] = df; sys.modules["dolfinx.common"] = common
-        b = types.ModuleType("fenics_constitutive._bindings")
-        for n in ("PyDruckerPrager3D", "PyDruckerPragerHyperbolic3D", "PyLinearElasticity3D", "PyMisesPlasticity3D"):
-            setattr(b, n, type(n, (), {}))
-        sys.modules["fenics_constitutive._bindings"] = b
-        sys.path.insert(0, "/root/reference/src")
+        import inspect, sys, types
+        from abc import ABC, abstractmethod
+        from enum import Enum
+        import numpy as np
         sys.path.insert(0, %r)
-        import fenics_constitutive.models as ref
+        z = np.load(%r)
+        names = [str(x) for x in z["constraint_names"]]
+        ssd = dict(zip(names, z["constraint_stress_strain_dim"].tolist()))
+        gd = dict(zip(names, z["constraint_geometric_dim"].tolist()))
+        Constraint = Enum("StressStrainConstraint", list(zip(names, z["constraint_values"].tolist())))
+        Constraint.stress_strain_dim = property(lambda self: ssd[self.name])
+        Constraint.geometric_dim = property(lambda self: gd[self.name])
+        abstract = {str(x) for x in z["abstract_members"]}
+        props = {str(x) for x in z["property_members"]}
+        params = [str(x) for x in z["evaluate_parameters"]]
+        body = {}
+        for name in sorted(abstract | props):
+            if name in abstract:
+                f = abstractmethod(lambda self, *a: None)
+            else:  # the concrete properties of the reference ABC: the dimensions of the model's constraint
+                f = (lambda attr: lambda self: getattr(self.constraint, attr))(name)
+            body[name] = property(f) if name in props else f
+        Model = type("IncrSmallStrainModel", (ABC,), body)
+        assert Model.__abstractmethods__ == frozenset(abstract), Model.__abstractmethods__
+        pkg, models, iface = (types.ModuleType(n) for n in ("fenics_constitutive", "fenics_constitutive.models",
+                                                            "fenics_constitutive.models.interfaces"))
+        iface.IncrSmallStrainModel, iface.StressStrainConstraint = Model, Constraint
+        pkg.models, models.interfaces = models, iface
+        sys.modules.update({m.__name__: m for m in (pkg, models, iface)})
         import fenics_constitutive_amd as fc
         from fenics_constitutive_amd import interfaces
         assert interfaces.REFERENCE_INTERFACES
-        assert fc.IncrSmallStrainModel is ref.IncrSmallStrainModel and fc.StressStrainConstraint is ref.StressStrainConstraint
+        assert fc.IncrSmallStrainModel is Model and fc.StressStrainConstraint is Constraint
         vm = fc.VonMises3D({"p_ka": 175000.0, "p_mu": 80769.0, "p_y0": 1200.0, "p_y00": 2500.0, "p_w": 200.0})
-        le = fc.LinearElasticityModel({"E": 42.0, "nu": 0.3}, ref.StressStrainConstraint.PLANE_STRESS)
-        assert isinstance(vm, ref.IncrSmallStrainModel) and isinstance(le, ref.IncrSmallStrainModel)
-        assert vm.constraint is ref.StressStrainConstraint.FULL and le.constraint is ref.StressStrainConstraint.PLANE_STRESS
-        assert vm.history_dim == ref.VonMises3D(dict(p_ka=1.0, p_mu=1.0, p_y0=1.0, p_y00=2.0, p_w=1.0)).history_dim
-        assert le.stress_strain_dim == 4 and le.geometric_dim == 2
+        le = fc.LinearElasticityModel({"E": 42.0, "nu": 0.3}, Constraint.PLANE_STRESS)
+        assert isinstance(vm, Model) and isinstance(le, Model)
+        assert vm.constraint is Constraint.FULL and le.constraint is Constraint.PLANE_STRESS
+        assert vm.history_dim == dict(zip([str(x) for x in z["von_mises_3d_history_keys"]], z["von_mises_3d_history_dims"].tolist()))
+        assert [le.stress_strain_dim, le.geometric_dim] == z["linear_elasticity_plane_stress_dims"].tolist() == [4, 2]
+        for law in (vm, le):  # the reference's call: evaluate(t, del_t, grad_del_u, stress, tangent, history)
+            assert list(inspect.signature(type(law).evaluate).parameters)[:len(params)] == params, inspect.signature(type(law).evaluate)
         print("drop-in ok")
         """
-    ) % ROOT
+    ) % (ROOT, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_interface.npz"))
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "drop-in ok" in r.stdout, r.stderr[-2000:]
 

@@ -13,6 +13,6 @@ for grp in "LDSBankConflict" "OccupancyPercent" "VALUBusy" "MemUnitBusy" "MemUni
            "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES" \
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" "TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
-  timeout 600 rocprofv3 --pmc $grp --output-format csv -d "$OUT/q_$i" -- python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline "$@" > "$OUT/q_$i.log" 2>&1
+  timeout 600 rocprofv3 --pmc $grp --output-format csv -d "$OUT/q_$i" -- python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --full "$@" > "$OUT/q_$i.log" 2>&1
   echo "$grp exit $?" >> "$OUT/q_$i.log"
 done

@@ -79,13 +79,13 @@ out = os.path.join(ROOT, "profiles", f"r{rnd}_{workload}_rocprof.md")
 with open(out, "w") as f:
     f.write(f"# rocprofv3 summary, round {rnd}, workload `{workload}`\n\n")
     if is_default:
-        f.write("Command (tools/profile_default.sh): `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py` "
+        f.write("Command (tools/profile_default.sh): `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full` "
                 "-- the driver's bench command (+ `--detail`, which only names where the full record is written): the headline workload, the five other "
                 "single-GPU configurations and the SURVEY 8(f) rows.\n\n")
     else:
         wl = next((workload[: -len(sfx)] for sfx in ("_full", "_unpacked", "_rows7") if workload.endswith(sfx)), workload)
         f.write("Command (tools/profile_gpu.sh): `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py "
-                f"--steps 10 --warmup 2 --no-cpu-baseline --workload {wl} {extra_args}` and one `--pmc FETCH_SIZE`, one "
+                f"--steps 10 --warmup 2 --no-cpu-baseline --full --workload {wl} {extra_args}` and one `--pmc FETCH_SIZE`, one "
                 "`--pmc WRITE_SIZE` pass (`--steps 4 --warmup 2`).\n\n")
     f.write("bench.py logs how many evaluate launches every phase issues (`launch_log`); the dispatches of the kernel trace are "
             "sliced with it.  Phases of one workload: 1 in-place warm step, the hipMalloc tangent candidates x 4 launches, the VMM "

@@ -9,7 +9,7 @@ for L in "$@"; do
     tag=$(basename "$L" .so)
     if [ "$L" = ship ]; then unset FCAMD_LIBRARY; else export FCAMD_LIBRARY=$R/$L; fi
     OUT=$R/gpurun_out/prof/valu_$tag; rm -rf "$OUT"; mkdir -p "$OUT"
-    timeout 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU --output-format csv -d "$OUT/q" -- python3 "$R/bench.py" --workload "$W" --steps 4 --warmup 1 --no-cpu-baseline --configs none --no-host-path --no-live-traffic --placement-tries 1 > "$OUT/log" 2>&1
+    timeout 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU --output-format csv -d "$OUT/q" -- python3 "$R/bench.py" --workload "$W" --steps 4 --warmup 1 --no-cpu-baseline --full --configs none --no-host-path --no-live-traffic --placement-tries 1 > "$OUT/log" 2>&1
     python3 - "$OUT" "$tag" <<'PY'
 import csv, glob, sys
 from collections import defaultdict
