@@ -20,7 +20,7 @@ from .models import (  # noqa: F401
     SpringMaxwellModel,
     VonMises3D,
 )
-from .wrappers import PlaneStrainFrom3D, UniaxialStrainFrom3D  # noqa: F401
+from .wrappers import PlaneStrainFrom3D, PlaneStressFrom3D, UniaxialStrainFrom3D, UniaxialStressFrom3D  # noqa: F401
 from .utils import get_elastic_tangent, get_identity, lame_parameters, strain_from_grad_u  # noqa: F401
 
 __version__ = "0.1.0"
@@ -38,6 +38,8 @@ __all__ = [
     "DruckerPragerHyperbolic3D",
     "UniaxialStrainFrom3D",
     "PlaneStrainFrom3D",
+    "UniaxialStressFrom3D",
+    "PlaneStressFrom3D",
     "lame_parameters",
     "get_elastic_tangent",
     "get_identity",

@@ -901,10 +901,16 @@ static int evaluate_wrapped(fcamd_model* m, int wrapper_constraint, double del_t
         return fail(FCAMD_ERR_UNSUPPORTED, "the fused 3D wrapper kernel exists for LinearElasticityModel and the plasticity laws");
     if (m->constraint != FCAMD_FULL)
         return fail(FCAMD_ERR_UNSUPPORTED, "the wrapped model must be a FULL (3-D) one");
-    const int wrap = wrapper_constraint == FCAMD_UNIAXIAL_STRAIN ? 1 : wrapper_constraint == FCAMD_PLANE_STRAIN ? 2 : 0;
-    if (!wrap) return fail(FCAMD_ERR_BAD_ARG, "wrapper constraint must be UNIAXIAL_STRAIN or PLANE_STRAIN");
+    // kernel wrap modes: 1 uniaxial strain, 2 plane strain, 3 plane stress, 4 uniaxial stress (fcamd_kernels.hip, kernels/stress_wrapped.h)
+    const int wrap = wrapper_constraint == FCAMD_UNIAXIAL_STRAIN ? 1
+                   : wrapper_constraint == FCAMD_PLANE_STRAIN    ? 2
+                   : wrapper_constraint == FCAMD_PLANE_STRESS    ? 3
+                   : wrapper_constraint == FCAMD_UNIAXIAL_STRESS ? 4
+                                                                 : 0;
+    if (!wrap) return fail(FCAMD_ERR_BAD_ARG, "wrapper constraint must be UNIAXIAL_STRAIN, PLANE_STRAIN, PLANE_STRESS or UNIAXIAL_STRESS");
     if (n > 0 && !stress_3d) return fail(FCAMD_ERR_BAD_ARG, "stress_3d is NULL");
-    if (!aligned16(stress_3d) || (wrap == 2 && (!aligned16(grad_lo) || !aligned16(stress_lo) || !aligned16(tangent_lo))))
+    const bool plane = wrap == 2 || wrap == 3;
+    if (!aligned16(stress_3d) || (plane && (!aligned16(grad_lo) || !aligned16(stress_lo) || !aligned16(tangent_lo))))
         return fail(FCAMD_ERR_ALIGN, "device arrays must be 16-byte aligned");
     for (int k = 0; k < m->info.n_hist; ++k)
         if (!aligned16(hist[k])) return fail(FCAMD_ERR_ALIGN, "device history arrays must be 16-byte aligned");

@@ -42,6 +42,7 @@
 #include "kernels/law_comfe_mises.h"
 #include "kernels/law_drucker_prager.h"
 #include "kernels/law_lowdim.h"
+#include "kernels/stress_wrapped.h"
 
 namespace fcamd {
 
@@ -245,11 +246,17 @@ __global__ void __launch_bounds__(kWave) evaluate_lowdim_tail_kernel(const EvalA
     tile_lowdim<LAW, DIMS, false, false>(a, &T, region, p0, (int)(a.n - p0), (int)threadIdx.x);
 }
 
-// Fused wrapper kernels (VonMises3D under UniaxialStrainFrom3D / PlaneStrainFrom3D).
+// Fused wrapper kernels: the 3-D laws under UniaxialStrainFrom3D / PlaneStrainFrom3D (WRAP 1 / 2) and under
+// PlaneStressFrom3D / UniaxialStressFrom3D (WRAP 3 / 4: the local Newton iteration of kernels/stress_wrapped.h).
+template <int WRAP>
+constexpr int kWrapRegion = WRAP >= 3 ? kStressWrapRegion : kRegionDoubles;
+
 template <int LAW, int WRAP, bool FULL, bool NT>
 __device__ __forceinline__ void run_wrapped_tile(ArgsRef a, const Tables* T, double* region, long long p0,
                                                  int npts, int lane, WaveStats& st) {
-    if constexpr (LAW == LAW_VM3D)
+    if constexpr (WRAP >= 3)
+        tile_stress_wrapped<LAW, WRAP, FULL, NT>(a, T, region, p0, npts, lane, st);
+    else if constexpr (LAW == LAW_VM3D)
         tile_von_mises_wrapped<WRAP, FULL, NT>(a, T, region, p0, npts, lane, st);
     else if constexpr (LAW == LAW_LE)
         tile_linear_elasticity_wrapped<WRAP, FULL, NT>(a, T, region, p0, npts, lane);
@@ -265,7 +272,7 @@ template <int LAW, int WRAP, bool NT>
 __global__ void __launch_bounds__(kBlock, (LAW >= LAW_COMFE_DP ? 3 : 4)) evaluate_wrapped_kernel(const EvalArgs) {
     ArgsRef a = kernel_args();
     __shared__ __attribute__((aligned(16))) Tables T;
-    __shared__ __attribute__((aligned(16))) double scratch[kWavesPerBlock][kRegionDoubles];
+    __shared__ __attribute__((aligned(16))) double scratch[kWavesPerBlock][kWrapRegion<WRAP>];
     stage_tables(a, &T);
     int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
@@ -284,7 +291,7 @@ template <int LAW, int WRAP>
 __global__ void __launch_bounds__(kWave) evaluate_wrapped_tail_kernel(const EvalArgs) {
     ArgsRef a = kernel_args();
     __shared__ __attribute__((aligned(16))) Tables T;
-    __shared__ __attribute__((aligned(16))) double region[kRegionDoubles];
+    __shared__ __attribute__((aligned(16))) double region[kWrapRegion<WRAP>];
     stage_tables(a, &T);
     const long long p0 = (a.n / kWave) * kWave;
     WaveStats st;
@@ -523,20 +530,25 @@ static hipError_t launch_wrapped(const EvalArgs& args, int grid, hipStream_t str
     return hipGetLastError();
 }
 
+template <int LAW>
+static hipError_t launch_wrapped_law(int wrap, const EvalArgs& args, int grid, hipStream_t stream) {
+    switch (wrap) {
+        case 1: return launch_wrapped<LAW, 1>(args, grid, stream);
+        case 2: return launch_wrapped<LAW, 2>(args, grid, stream);
+        case 3: return launch_wrapped<LAW, 3>(args, grid, stream);
+        case 4: return launch_wrapped<LAW, 4>(args, grid, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
 hipError_t launch_evaluate_wrapped(int law, int wrap, const EvalArgs& args, int grid, hipStream_t stream) {
     if (args.n <= 0) return hipSuccess;
-    if (wrap != 1 && wrap != 2) return hipErrorInvalidValue;
     switch (law) {
-        case LAW_VM3D: return wrap == 1 ? launch_wrapped<LAW_VM3D, 1>(args, grid, stream) : launch_wrapped<LAW_VM3D, 2>(args, grid, stream);
-        case LAW_LE: return wrap == 1 ? launch_wrapped<LAW_LE, 1>(args, grid, stream) : launch_wrapped<LAW_LE, 2>(args, grid, stream);
-        case LAW_COMFE_MISES:
-            return wrap == 1 ? launch_wrapped<LAW_COMFE_MISES, 1>(args, grid, stream)
-                             : launch_wrapped<LAW_COMFE_MISES, 2>(args, grid, stream);
-        case LAW_COMFE_DP:
-            return wrap == 1 ? launch_wrapped<LAW_COMFE_DP, 1>(args, grid, stream) : launch_wrapped<LAW_COMFE_DP, 2>(args, grid, stream);
-        case LAW_COMFE_DP_HYPER:
-            return wrap == 1 ? launch_wrapped<LAW_COMFE_DP_HYPER, 1>(args, grid, stream)
-                             : launch_wrapped<LAW_COMFE_DP_HYPER, 2>(args, grid, stream);
+        case LAW_VM3D: return launch_wrapped_law<LAW_VM3D>(wrap, args, grid, stream);
+        case LAW_LE: return launch_wrapped_law<LAW_LE>(wrap, args, grid, stream);
+        case LAW_COMFE_MISES: return launch_wrapped_law<LAW_COMFE_MISES>(wrap, args, grid, stream);
+        case LAW_COMFE_DP: return launch_wrapped_law<LAW_COMFE_DP>(wrap, args, grid, stream);
+        case LAW_COMFE_DP_HYPER: return launch_wrapped_law<LAW_COMFE_DP_HYPER>(wrap, args, grid, stream);
         default: return hipErrorInvalidValue;
     }
 }

@@ -15,7 +15,9 @@ namespace fcamd {
 // cached 3-D stress row, runs the law's update on the padded point, and writes the full row back to
 // the cache and the mapped components to the caller's arrays.  No 3-D gradient or tangent array
 // exists.  WRAP = 1: component 11 of everything; WRAP = 2: gradient (0,1,2,3) -> (0,1,3,4), Mandel
-// components 0..3, tangent block [0:4, 0:4] (utils.py:282-297, 377-412).  In place only (the wrappers
+// components 0..3, tangent block [0:4, 0:4] (utils.py:282-297, 377-412).  The stress wrappers (stress_wrapped.h)
+// load and store through the same functions: WRAP = 3 (plane stress) maps as WRAP = 2, WRAP = 4 (uniaxial stress)
+// as WRAP = 1.  In place only (the wrappers
 // have no out-of-place form).  The per-point arithmetic is the 3-D tiles' own (vm_trial / vm_return / vm_stress,
 // cm_point, dp_trial / dp_return); tests/test_gpu_wrappers.py holds wrapper and 3-D law to bit equality.
 
@@ -23,14 +25,14 @@ namespace fcamd {
 template <int WRAP, bool FULL, bool NT>
 __device__ __forceinline__ void wrapped_load(ArgsRef a, double* region, long long p0, int npts, int lane,
                                              double (&g)[9], double (&s)[6]) {
-    constexpr int LD = WRAP == 1 ? 1 : 4;  // doubles per point of the low-dimensional gradient and stress
+    constexpr int LD = (WRAP == 1 || WRAP == 4) ? 1 : 4;  // doubles per point of the low-dimensional gradient and stress
     const bool live = FULL || lane < npts;
     Chunks<6> cc;
     tile_load<6, FULL, NT>(cc, a.cache3d + p0 * 6, npts * 6, lane);
 #pragma unroll
     for (int i = 0; i < 9; ++i) g[i] = 0.0;
     double s_lo[LD];
-    if constexpr (WRAP == 1) {
+    if constexpr (LD == 1) {
         g[0] = live ? a.grad[p0 + lane] : 0.0;
         s_lo[0] = live ? a.stress_in[p0 + lane] : 0.0;
     } else {
@@ -52,12 +54,12 @@ template <int WRAP, bool FULL, bool NT>
 __device__ __forceinline__ void wrapped_store_stress(ArgsRef a, double* region, long long p0, int npts,
                                                      int lane, const double (&s)[6]) {
     transpose_out<6, FULL, NT>(s, region, lane, a.cache3d + p0 * 6, npts * 6);
-    if constexpr (WRAP == 1) {
+    if constexpr (WRAP == 1 || WRAP == 4) {
         if (FULL || lane < npts) a.stress_out[p0 + lane] = s[0];
     } else {
         double s_lo[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) s_lo[i] = s[i];
+        for (int i = 0; i < 4; ++i) s_lo[i] = (WRAP == 3 && i == 2) ? 0.0 : s[i];  // plane stress: the constrained zz is exactly 0
         transpose_out<4, FULL, NT>(s_lo, region, lane, a.stress_out + p0 * 4, npts * 4);
     }
 }

@@ -13,6 +13,11 @@ gradient or tangent array:
 
 The history dict must be of the same kind as the other arrays (NumPy history is staged per
 call like the reference's in-place arrays).
+
+``PlaneStressFrom3D`` / ``UniaxialStressFrom3D`` (no counterpart in the reference) solve, per point, for the
+out-of-plane strain increments that make the constrained stresses vanish: a local Newton iteration around the
+3-D law ("The f3 stress wrappers"), fused into one kernel for the same laws, and an array-level Newton
+iteration around the 3-D model's own ``evaluate`` otherwise.
 """
 
 from __future__ import annotations
@@ -25,7 +30,7 @@ from . import _capi
 from .device import _check_torch, _current_stream_ptr, _is_torch
 from .interfaces import IncrSmallStrainModel, StressStrainConstraint
 
-__all__ = ["UniaxialStrainFrom3D", "PlaneStrainFrom3D"]
+__all__ = ["UniaxialStrainFrom3D", "PlaneStrainFrom3D", "UniaxialStressFrom3D", "PlaneStressFrom3D"]
 
 
 class _From3D(IncrSmallStrainModel):
@@ -103,11 +108,16 @@ class _From3D(IncrSmallStrainModel):
         k_g, k_s, k_sb, k_tb = self._kinds
         self._convert(ctx, k_g, n, g_lo, self.grad_del_u_3d)
         self._convert(ctx, k_s, n, s_lo, self.stress_3d)
+        self._evaluate_3d(ctx, t, del_t, n, s_lo, t_lo, h_dev)
+        if host:
+            self._download(stress, tangent, history, s_lo, t_lo, h_dev)
+
+    def _evaluate_3d(self, ctx, t, del_t, n, s_lo, t_lo, h_dev):
+        """generic path, after the mapped components are in the cached 3-D arrays: evaluate, map back"""
+        k_g, k_s, k_sb, k_tb = self._kinds
         self.model.evaluate(t, del_t, self.grad_del_u_3d, self.stress_3d, self.tangent_3d, h_dev)
         self._convert(ctx, k_tb, n, self.tangent_3d, t_lo)
         self._convert(ctx, k_sb, n, self.stress_3d, s_lo)
-        if host:
-            self._download(stress, tangent, history, s_lo, t_lo, h_dev)
 
     @staticmethod
     def _download(stress, tangent, history, s_lo, t_lo, h_dev):
@@ -134,3 +144,137 @@ class PlaneStrainFrom3D(_From3D):
 
     _constraint = StressStrainConstraint.PLANE_STRAIN
     _kinds = (_capi.GRAD_2D_TO_3D, _capi.STRESS_2D_TO_3D, _capi.STRESS_3D_TO_2D, _capi.TANGENT_3D_TO_2D)
+
+
+# local Newton iteration of the stress wrappers: the rule of the fused kernel (kernels/stress_wrapped.h)
+STRESS_WRAP_RTOL = 1e-12
+STRESS_WRAP_MAX_ITER = 50
+
+
+def _isotropic_tangent(kappa: float, mu: float) -> np.ndarray:
+    xioi = np.zeros((6, 6))
+    xioi[:3, :3] = 1.0
+    return kappa * xioi + 2.0 * mu * (np.eye(6) - xioi / 3.0)
+
+
+def _elastic_tangent_3d(model):
+    """the 3-D law's elastic tangent (Mandel), or None where it has none independent of the state (the SLS laws: the
+    local iteration then starts from a zero increment; their update is linear in it, one Newton step solves it)"""
+    mid = getattr(model, "_model_id", None)
+    if mid == _capi.LINEAR_ELASTICITY:
+        return np.asarray(model.D, dtype=np.float64)
+    if mid == _capi.VON_MISES_3D:
+        return _isotropic_tangent(model.p_ka, model.p_mu)
+    if mid in (_capi.COMFE_LINEAR_ELASTICITY, _capi.COMFE_MISES_PLASTICITY, _capi.COMFE_DRUCKER_PRAGER,
+               _capi.COMFE_DRUCKER_PRAGER_HYPERBOLIC):
+        mu, kappa = model._parameter_vector[:2]
+        return _isotropic_tangent(kappa, mu)
+    return None
+
+
+def _solve_bb(c, r):
+    """C_bb^-1 r per point, closed form (1x1 or 2x2, the kernel's expressions): c (n, k, k), r (n, k)"""
+    if c.shape[1] == 1:
+        return r / c[:, 0]
+    c11, c12, c21, c22 = c[:, 0, 0], c[:, 0, 1], c[:, 1, 0], c[:, 1, 1]
+    det = c11 * c22 - c12 * c21
+    r1, r2 = r[:, 0], r[:, 1]
+    import torch
+
+    return torch.stack(((c22 * r1 - c12 * r2) / det, (c11 * r2 - c21 * r1) / det), dim=1)
+
+
+class _StressFrom3D(_From3D):
+    #: Mandel components whose stress is held at zero (the unknown strain increments) and their 3-D gradient entries
+    _free: tuple[int, ...]
+    _free_grad: tuple[int, ...]
+
+    def _evaluate_3d(self, ctx, t, del_t, n, s_lo, t_lo, h_dev):
+        """Generic path: the fused kernel's local Newton iteration as an array-level one around the 3-D model's own
+        evaluate.  Every iteration starts from the committed stress and history; a point's increment is frozen once it
+        has converged (or failed), so the last evaluation -- which every point takes part in -- holds every point's
+        converging iterate."""
+        import torch
+
+        dev = self.stress_3d.device
+        g3, s3 = self.grad_del_u_3d.view(n, 9), self.stress_3d.view(n, 6)
+        tan3 = self.tangent_3d.view(n, 6, 6)
+        b, gb = list(self._free), list(self._free_grad)
+        s0 = s3.clone()
+        h0 = None if h_dev is None else {k: v.clone() for k, v in h_dev.items()}
+        ce = _elastic_tangent_3d(self.model)
+        if ce is None:
+            delta = torch.zeros((n, len(b)), dtype=torch.float64, device=dev)
+        else:
+            # C^e_bb d = -(sigma0_b + C^e_ba d_eps_a); the mapped normal strains are g[0] (and g[4] under plane stress),
+            # the isotropic elastic tangents couple no shear into the normal stresses
+            ce_t = torch.from_numpy(ce).to(dev)
+            rhs = s0[:, b] + g3[:, 0:1] * ce_t[b, 0]
+            if 1 not in b:
+                rhs = rhs + g3[:, 4:5] * ce_t[b, 1]
+            delta = -_solve_bb(ce_t[b][:, b].expand(n, len(b), len(b)), rhs)
+        done = torch.zeros(n, dtype=torch.bool, device=dev)
+        failed = torch.zeros(n, dtype=torch.bool, device=dev)
+        for evals in range(1, STRESS_WRAP_MAX_ITER + 1):
+            g3[:, gb] = delta
+            s3.copy_(s0)
+            if h0 is not None:
+                for k in h_dev:
+                    h_dev[k].copy_(h0[k])
+            self.model.evaluate(t, del_t, self.grad_del_u_3d, self.stress_3d, self.tangent_3d, h_dev)
+            r = s3[:, b]
+            conv = (r == 0).all(dim=1) | (r.abs().amax(dim=1) <= STRESS_WRAP_RTOL * torch.linalg.vector_norm(s3, dim=1))
+            done |= conv
+            if bool(done.all()):
+                break
+            if evals == STRESS_WRAP_MAX_ITER:
+                failed |= ~done
+                break
+            nd = delta - _solve_bb(tan3[:, b][:, :, b], r)
+            bad = ~done & ~torch.isfinite(nd).all(dim=1)
+            failed |= bad
+            done |= bad
+            delta = torch.where(done[:, None], delta, nd)
+        if bool(failed.any()):
+            raise RuntimeError(f"{type(self).__name__}: the local Newton iteration did not converge at {int(failed.sum())} points")
+        self._condense(n, s_lo, t_lo)
+
+    def _condense(self, n, s_lo, t_lo):
+        s3, tan3 = self.stress_3d.view(n, 6), self.tangent_3d.view(n, 6, 6)
+        if self._constraint == StressStrainConstraint.PLANE_STRESS:
+            c = tan3[:, :4, :4]
+            u = c[:, :, 2] / c[:, 2, 2][:, None]
+            ct = c - u[:, :, None] * c[:, 2, None, :]
+            ct[:, 2, :] = 0.0
+            ct[:, :, 2] = 0.0
+            t_lo.view(n, 4, 4).copy_(ct)
+            s_lo.view(n, 4).copy_(s3[:, :4])
+            s_lo.view(n, 4)[:, 2] = 0.0
+        else:
+            c = tan3
+            c11, c12, c21, c22, c10, c20 = c[:, 1, 1], c[:, 1, 2], c[:, 2, 1], c[:, 2, 2], c[:, 1, 0], c[:, 2, 0]
+            det = c11 * c22 - c12 * c21
+            y1, y2 = (c22 * c10 - c12 * c20) / det, (c11 * c20 - c21 * c10) / det
+            t_lo.copy_(c[:, 0, 0] - (c[:, 0, 1] * y1 + c[:, 0, 2] * y2))
+            s_lo.copy_(s3[:, 0])
+
+
+class UniaxialStressFrom3D(_StressFrom3D):
+    """Drive a 3-D model under uniaxial stress: component 11 of gradient, stress and tangent; the lateral strain
+    increments d_eps_yy, d_eps_zz are solved per point so that sigma_yy = sigma_zz = 0.  The tangent is the condensed
+    d sigma_xx / d eps_xx.  Shear stresses are not enforced (they stay zero for the isotropic laws from a zero cache)."""
+
+    _constraint = StressStrainConstraint.UNIAXIAL_STRESS
+    _kinds = (_capi.GRAD_1D_TO_3D, _capi.STRESS_1D_TO_3D, _capi.STRESS_3D_TO_1D, _capi.TANGENT_3D_TO_1D)
+    _free, _free_grad = (1, 2), (4, 8)
+
+
+class PlaneStressFrom3D(_StressFrom3D):
+    """Drive a 3-D model under plane stress: gradient components (0,1,2,3)->(0,1,3,4), Mandel components 0..3 as under
+    plane strain; the out-of-plane strain increment d_eps_zz is solved per point so that sigma_zz = 0.  The returned
+    sigma_zz is exactly 0 and the 4x4 tangent is the condensed one, C_aa - C_az C_zz^-1 C_za, with its zz row and column
+    exactly 0.  The out-of-plane shear stresses are not enforced."""
+
+    _constraint = StressStrainConstraint.PLANE_STRESS
+    _kinds = (_capi.GRAD_2D_TO_3D, _capi.STRESS_2D_TO_3D, _capi.STRESS_3D_TO_2D, _capi.TANGENT_3D_TO_2D)
+    _free, _free_grad = (2,), (8,)

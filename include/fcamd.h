@@ -200,12 +200,31 @@ FCAMD_API int fcamd_evaluate_host(fcamd_model* model, double t, double del_t, in
                      fused form of the reference's 3D -> 1D/2D wrappers around LinearElasticityModel and the
                      plasticity laws (UniaxialStrainFrom3D / PlaneStrainFrom3D, models/utils.py:211-412):
                      grad_del_u, stress, tangent are the LOW-dimensional arrays (1 / 1 / 1 doubles per point for
-                     FCAMD_UNIAXIAL_STRAIN, 4 / 4 / 16 for FCAMD_PLANE_STRAIN), stress_3d (6 n) is the wrapper's
+                     FCAMD_UNIAXIAL_STRAIN and FCAMD_UNIAXIAL_STRESS, 4 / 4 / 16 for FCAMD_PLANE_STRAIN and
+                     FCAMD_PLANE_STRESS), stress_3d (6 n) is the wrapper's
                      cached 3-D stress whose unmapped components persist from call to call (utils.py:253-266;
                      zero-initialised by the caller), the history is the 3-D law's, everything in place
                      (stress_prev == stress, history_prev == history).  One kernel replaces map -> evaluate -> map;
                      no 3-D gradient or tangent array exists.  Other laws: FCAMD_ERR_UNSUPPORTED (use
-                     fcamd_convert_device around the plain call);
+                     fcamd_convert_device around the plain call).
+                     FCAMD_PLANE_STRESS / FCAMD_UNIAXIAL_STRESS (PlaneStressFrom3D / UniaxialStressFrom3D, no
+                     counterpart in the reference): per point, a local Newton iteration solves for the out-of-plane
+                     strain increments (plane stress: d_eps_zz, the 2-D gradient mapped as under plane strain;
+                     uniaxial stress: d_eps_yy, d_eps_zz) that make the constrained Mandel stresses vanish.  The
+                     committed state is the cached 3-D stress row with the mapped components (Mandel 0..3 / 0) from
+                     `stress`, and the law's history.  Start: the elastic condensation C^e_bb d = -(sigma0_b +
+                     C^e_ba d_eps_a) with the law's elastic tangent (an elastic point costs one law evaluation).
+                     Every iteration evaluates the 3-D update from the committed state; converged when
+                     max|sigma_b| <= 1e-12 |sigma|_2 (Mandel norm of the iterate) or sigma_b == 0, else
+                     d <- d - C_bb^-1 sigma_b with that iterate's consistent tangent.  A point still unconverged
+                     after 50 evaluations, or whose step is not finite (singular C_bb), counts as non-converged
+                     (FCAMD_ERR_NONCONVERGED through the counters, like the law's own).  Outputs are those of the
+                     last evaluated iterate: history, the full 3-D row in stress_3d, the mapped stresses with the
+                     plane-stress zz written as exactly 0.0, and the condensed tangent C_aa - C_ab C_bb^-1 C_ba
+                     (plane stress: zz row and column exactly 0).  The law's Newton-iteration counter accumulates
+                     over all local iterations, the plastic count is the last iterate's.  Out-of-plane shear
+                     stresses are not enforced: they are unmapped components of the cache (zero for the isotropic
+                     laws from a zero cache).  Any other wrapper_constraint: FCAMD_ERR_BAD_ARG;
      flags           FCAMD_EVAL_* below. */
 typedef struct fcamd_eval_args {
     const double* grad_del_u;
@@ -227,7 +246,8 @@ typedef struct fcamd_eval_args {
                                            handle cannot read each other's non-convergence */
     const uint64_t* packed_mask_prev;   /* FCAMD_EVAL_PACKED_HISTORY: the EVER mask of the committed plastic-strain array, */
     uint64_t* packed_mask;              /* ... of the trial array (written); one word per 64-point tile each */
-    int wrapper_constraint;             /* 0, or FCAMD_UNIAXIAL_STRAIN / FCAMD_PLANE_STRAIN: the fused 3D wrapper form */
+    int wrapper_constraint;             /* 0, or FCAMD_UNIAXIAL_STRAIN / FCAMD_PLANE_STRAIN / FCAMD_PLANE_STRESS /
+                                           FCAMD_UNIAXIAL_STRESS: the fused 3D wrapper form */
     double* stress_3d;                  /* the wrapper's cached 3-D stress (6 n), with wrapper_constraint */
 } fcamd_eval_args;
 /* Layout of a counter buffer: FCAMD_COUNTER_SLOTS slots of 4 words {non-converged points, plastic

@@ -10,7 +10,9 @@ LAWS = {"VonMises3D": lambda: fc.VonMises3D({"p_ka": 175000.0, "p_mu": 80769.0, 
 lname = sys.argv[2] if len(sys.argv) > 2 else "VonMises3D"
 fused = not (len(sys.argv) > 3 and sys.argv[3] == "generic")
 vm = LAWS[lname]()
-for name, W, gd2, sd in (("plane_strain", fc.PlaneStrainFrom3D, 4, 4), ("uniaxial_strain", fc.UniaxialStrainFrom3D, 1, 1)):
+# the strain wrappers and the stress wrappers (local Newton iteration per point) on the same arrays: same bytes moved
+for name, W, gd2, sd in (("plane_strain", fc.PlaneStrainFrom3D, 4, 4), ("uniaxial_strain", fc.UniaxialStrainFrom3D, 1, 1),
+                         ("plane_stress", fc.PlaneStressFrom3D, 4, 4), ("uniaxial_stress", fc.UniaxialStressFrom3D, 1, 1)):
     w = W(vm)
     w.fused = fused
     gen = torch.Generator(device=dev).manual_seed(1)
@@ -36,6 +38,9 @@ for name, W, gd2, sd in (("plane_strain", fc.PlaneStrainFrom3D, 4, 4), ("uniaxia
         a.record(); w.evaluate(0.0, 1.0, g, s, t, h); b.record()
     torch.cuda.synchronize()
     ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
-    print(json.dumps({"law": lname, "fused": fused, "wrapper": name, "n": n, "ms": round(ms, 3), "Gpts_s": round(n / ms / 1e6, 2), "plastic": int(vm.device_stats().n_plastic)}), flush=True)
+    st = vm.device_stats()  # counters of the last call: plastic points, Newton iterations (stress wrappers: over all local iterations)
+    print(json.dumps({"law": lname, "fused": fused, "wrapper": name, "n": n, "ms": round(ms, 3), "Gpts_s": round(n / ms / 1e6, 2),
+                      "plastic": int(st.n_plastic), "plastic_fraction": round(st.n_plastic / n, 4),
+                      "inner_iters_per_plastic": round(st.n_newton_iters / max(st.n_plastic, 1), 3)}), flush=True)
     del w, g, s, s0, t, h, h0
     torch.cuda.empty_cache()
