@@ -19,7 +19,7 @@ SOURCES = ["fcamd_kernels.hip", "fcamd_aux_kernels.hip", "fcamd_capi.cpp", "fcam
 # the device code lives in per-law headers that fcamd_kernels.hip includes
 KERNEL_HEADERS = [os.path.join("kernels", h) for h in (
     "tile_io.h", "tangent_writers.h", "wrapped_io.h", "history_rows.h", "law_linear_elasticity.h", "law_sls.h",
-    "law_von_mises.h", "law_comfe_mises.h", "law_drucker_prager.h", "law_lowdim.h", "stress_wrapped.h")]
+    "law_von_mises.h", "law_comfe_mises.h", "law_drucker_prager.h", "law_lowdim.h", "stress_wrapped.h", "param_source.h")]
 HEADERS = ["fcamd_internal.h", "fcamd_host.h", os.path.join("..", "..", "include", "fcamd.h"), os.path.join("..", "..", "include", "fcamd_multi.h"), *KERNEL_HEADERS]
 ARCH = "gfx950"
 # -ffp-contract=off: arithmetic order is part of the parity contract (see fcamd_kernels.hip)

@@ -29,6 +29,7 @@ COUNTER_SLOTS, COUNTER_WORDS = 64, 256  # FCAMD_COUNTER_SLOTS / FCAMD_COUNTER_WO
 EVAL_SPARSE_TANGENT = 1
 EVAL_SPLIT_HISTORY = 4
 EVAL_PACKED_HISTORY = 8
+EVAL_PARAM_FIELDS = 16  # per-point parameters: the field table travels in fcamd_eval_args.stress_3d
 
 # context option "last_host_mode": FCAMD_HOST_* flags (include/fcamd.h)
 HOST_ZERO_COPY_IN, HOST_ZERO_COPY_OUT, HOST_TEMP_LOCK, HOST_BOUNCE = 1, 2, 4, 8
@@ -70,6 +71,15 @@ class EvalArgs(C.Structure):
                 ("n_hist", C.c_int), ("parent_rows", C.c_void_p), ("history_mask", C.c_void_p), ("flags", C.c_int), ("stress2", C.c_void_p),
                 ("counters", C.c_void_p), ("packed_mask_prev", C.c_void_p), ("packed_mask", C.c_void_p),
                 ("wrapper_constraint", C.c_int), ("stress_3d", C.c_void_p)]
+
+
+def set_param_fields(x: EvalArgs, table) -> None:
+    """the header's fcamd_eval_args_set_param_fields: ``table`` (ctypes array of device addresses, one per parameter; kept alive by
+    the caller) as the call's per-point parameters, or None"""
+    if table is None:
+        return
+    x.stress_3d = C.addressof(table)
+    x.flags = int(x.flags) | EVAL_PARAM_FIELDS
 
 
 class ModelInfo(C.Structure):
@@ -702,17 +712,23 @@ class Model:
 
     def evaluate_device_ex(self, t, del_t, n, grad_ptr, stress_prev_ptr, stress_ptr, tangent_ptr, hist_prev_ptrs,
                            hist_ptrs, rows_ptr=None, mask_ptr=None, flags: int = 0, stress2_ptr=None,
-                           counters_ptr=None, packed_mask_ptrs=None, wrapper_constraint: int = 0, stress3d_ptr=None) -> None:
+                           counters_ptr=None, packed_mask_ptrs=None, wrapper_constraint: int = 0, stress3d_ptr=None,
+                           field_ptrs=None) -> None:
         """``fcamd_evaluate_device_ex``: THE device entry, every form of the call in one argument struct.  Inside a
         ``batched_launches()`` block the call is recorded and leaves with the block's other calls as ONE
-        ``fcamd_evaluate_batch``."""
+        ``fcamd_evaluate_batch``.  ``field_ptrs``: one device address (or 0) per parameter of the model
+        (FCAMD_EVAL_PARAM_FIELDS); such a call is never batched."""
         arr, nh = self._ptr_array(hist_ptrs)
         parr, _ = self._ptr_array(hist_prev_ptrs)
+        farr, _ = self._ptr_array(field_ptrs)
         pm_prev, pm = packed_mask_ptrs or (None, None)
         x = EvalArgs(grad_ptr, stress_prev_ptr, stress_ptr, tangent_ptr or None, parr, arr, nh, rows_ptr or None,
                      mask_ptr or None, int(flags), stress2_ptr or None, counters_ptr or None, pm_prev or None, pm or None,
                      int(wrapper_constraint), stress3d_ptr or None)
+        set_param_fields(x, farr)
         batch = getattr(_tls, "batch", None)
+        if batch is not None and farr is not None:
+            raise NotImplementedError("batched_launches: laws with per-point parameter fields are not batched")
         if batch is not None and not wrapper_constraint:
             batch.add(self, float(t), float(del_t), int(n), x, (arr, parr))
             return
@@ -731,12 +747,14 @@ class Model:
         check(self._lib.fcamd_evaluate_device_ex(self.handle, float(t), float(del_t), int(n), C.byref(x)))
 
     def evaluate_resident(self, t, del_t, n, grad_host_ptr, stress_prev_ptr, stress_ptr, hist_prev_ptrs, hist_ptrs,
-                          mask_ptr, stress_host_ptr, tangent_host_ptr, flags: int = 0, packed_mask_ptrs=None) -> Stats:
+                          mask_ptr, stress_host_ptr, tangent_host_ptr, flags: int = 0, packed_mask_ptrs=None, field_ptrs=None) -> Stats:
         arr, nh = self._ptr_array(hist_ptrs)
         parr, _ = self._ptr_array(hist_prev_ptrs)
+        farr, _ = self._ptr_array(field_ptrs)
         pm_prev, pm = packed_mask_ptrs or (None, None)
         x = EvalArgs(grad_host_ptr, stress_prev_ptr, stress_ptr, None, parr, arr, nh, None, mask_ptr or None, int(flags), None, None,
                      pm_prev or None, pm or None, 0, None)
+        set_param_fields(x, farr)
         st = Stats()
         _flush_recorded()
         status = self._lib.fcamd_evaluate_resident(self.handle, float(t), float(del_t), int(n), C.byref(x),

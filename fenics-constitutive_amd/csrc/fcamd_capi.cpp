@@ -441,13 +441,58 @@ static void fill_args(fcamd_model* m, double del_t, int64_t n, const double* gra
     a.tb = m->tb;
 }
 
+const double* const* fields_of(const fcamd_eval_args* x) {
+    return (x->flags & FCAMD_EVAL_PARAM_FIELDS) ? reinterpret_cast<const double* const*>(x->stress_3d) : nullptr;
+}
+
+bool has_fields(const fcamd_model* m, const double* const* fields) {
+    if (!fields) return false;
+    for (int k = 0; k < m->info.n_params; ++k)
+        if (fields[k]) return true;
+    return false;
+}
+
+// the checks of a call with per-point parameters (parent_rows / wrapper forms are refused by the callers)
+int check_fields(const fcamd_model* m, const double* const* fields) {
+    if (!has_fields(m, fields)) return FCAMD_OK;
+    if (!law_has_field_kernels(m->law) || m->constraint != FCAMD_FULL)
+        return fail(FCAMD_ERR_UNSUPPORTED, "per-point parameter fields exist for LinearElasticityModel (FULL), LinearElasticity3D, VonMises3D "
+                                           "and MisesPlasticityLinearHardening3D (model %d, constraint %d)", m->law, m->constraint);
+    for (int k = 0; k < m->info.n_params; ++k)
+        if (!aligned16(fields[k])) return fail(FCAMD_ERR_ALIGN, "parameter field %d must be 16-byte aligned", k);
+    return FCAMD_OK;
+}
+
+// the launch's FieldArgs: the fields shifted to the launch's first point, the model's own parameters behind them
+static void field_args_for(const fcamd_model* m, const double* const* fields, int64_t p0, FieldArgs& f) {
+    std::memset(&f, 0, sizeof(f));
+    for (int k = 0; k < m->info.n_params; ++k) {
+        f.f[k] = fields[k] ? fields[k] + p0 : nullptr;
+        f.v[k] = m->params[k];
+    }
+}
+
+// the tables of a field launch: the Mises laws scale table a (ka xioi, kappa soo) per point -- it holds the unit pattern instead
+static void field_tables(const fcamd_model* m, EvalArgs& a) {
+    if (m->law != FCAMD_VON_MISES_3D && m->law != FCAMD_COMFE_MISES_PLASTICITY) return;
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) a.tb.a[6 * i + j] = (i < 3 && j < 3) ? 1.0 : 0.0;
+}
+
 int enqueue(fcamd_model* m, double del_t, int64_t n, const double* grad, const double* stress_prev,
             double* stress, double* tangent, const double* const* hprev, double* const* hcur,
             hipStream_t stream, bool reset_counters, const int* rows,
             unsigned long long* hmask, int flags, double* stress2,
-            unsigned long long* counters, const unsigned long long* emask_prev, unsigned long long* emask) {
+            unsigned long long* counters, const unsigned long long* emask_prev, unsigned long long* emask,
+            const double* const* fields, int64_t field_p0) {
     EvalArgs a;
     fill_args(m, del_t, n, grad, stress_prev, stress, tangent, hprev, hcur, rows, hmask, flags, stress2, counters, emask_prev, emask, a);
+    const bool per_point = has_fields(m, fields);
+    if (per_point) {  // (the twin is a measurement device of the scalar kernel)
+        a.flags &= ~64;
+        a.cache3d = nullptr;
+        field_tables(m, a);
+    }
     // only the plasticity laws count anything: skip the extra launch for the others
     if ((reset_counters || counters) && law_counts(m->law)) HIP_TRY(hipMemsetAsync(a.counters, 0, kCounterBytes, stream));
     if (n == 0) return FCAMD_OK;
@@ -455,6 +500,12 @@ int enqueue(fcamd_model* m, double del_t, int64_t n, const double* grad, const d
     // the launchers report hipGetLastError(): drop whatever an earlier, unrelated call of this thread
     // (ours, the caller's, torch's) left behind, so that a failure reported here is this launch's
     (void)hipGetLastError();
+    if (per_point) {
+        FieldArgs f;
+        field_args_for(m, fields, field_p0, f);
+        HIP_TRY(launch_evaluate_fields(m->law, a, f, grid, stream));
+        return FCAMD_OK;
+    }
     HIP_TRY(launch_evaluate(m->law, m->dims.gdim, a, grid, stream));
     return FCAMD_OK;
 }
@@ -721,10 +772,15 @@ static int check_device_ex(fcamd_model* m, double del_t, int64_t n, const fcamd_
                            reinterpret_cast<const void* const*>(x->history_prev),
                            reinterpret_cast<const void* const*>(x->history), x->n_hist, x->flags);
     if (st != FCAMD_OK) return st;
-    if (x->flags & ~(FCAMD_EVAL_SPARSE_TANGENT | FCAMD_EVAL_SPLIT_HISTORY | FCAMD_EVAL_PACKED_HISTORY))
+    if (x->flags & ~(FCAMD_EVAL_SPARSE_TANGENT | FCAMD_EVAL_SPLIT_HISTORY | FCAMD_EVAL_PACKED_HISTORY | FCAMD_EVAL_PARAM_FIELDS))
         return fail(FCAMD_ERR_UNSUPPORTED, "unknown FCAMD_EVAL_* flag in 0x%x (2, FCAMD_EVAL_DELTA_HISTORY of ABI 0.3, was removed in 0.4)", x->flags);
     if (x->parent_rows && m->constraint != FCAMD_FULL)
         return fail(FCAMD_ERR_UNSUPPORTED, "the indexed form exists for StressStrainConstraint.FULL only");
+    if (has_fields(m, fields_of(x))) {
+        if (x->parent_rows) return fail(FCAMD_ERR_UNSUPPORTED, "per-point parameter fields: the indexed form (parent_rows) is not supported");
+        st = check_fields(m, fields_of(x));
+        if (st != FCAMD_OK) return st;
+    }
     if (x->history_mask && !has_sparse_history(m->law))
         return fail(FCAMD_ERR_UNSUPPORTED, "sparse trial history exists for the plasticity laws only");
     if ((x->flags & FCAMD_EVAL_SPARSE_TANGENT) && (!x->history_mask || !x->tangent))
@@ -760,13 +816,16 @@ static int enqueue_ex(fcamd_model* m, double del_t, int64_t n, const fcamd_eval_
                    stream, reset_counters, x->parent_rows, reinterpret_cast<unsigned long long*>(x->history_mask), x->flags,
                    x->stress2, reinterpret_cast<unsigned long long*>(x->counters),
                    (x->flags & FCAMD_EVAL_PACKED_HISTORY) ? reinterpret_cast<const unsigned long long*>(x->packed_mask_prev) : nullptr,
-                   (x->flags & FCAMD_EVAL_PACKED_HISTORY) ? reinterpret_cast<unsigned long long*>(x->packed_mask) : nullptr);
+                   (x->flags & FCAMD_EVAL_PACKED_HISTORY) ? reinterpret_cast<unsigned long long*>(x->packed_mask) : nullptr,
+                   fields_of(x), 0);
 }
 
 int fcamd_evaluate_device_ex(fcamd_model* m, double t, double del_t, int64_t n, const fcamd_eval_args* x) {
     (void)t;
     if (!x) return fail(FCAMD_ERR_BAD_ARG, "args is NULL");
     if (x->wrapper_constraint != 0) {  // the fused 3D -> 1D/2D wrapper form
+        if (x->flags & FCAMD_EVAL_PARAM_FIELDS)
+            return fail(FCAMD_ERR_UNSUPPORTED, "per-point parameter fields: the fused wrapper form is not supported");
         if (x->parent_rows || x->history_mask || x->stress2 || x->counters || x->flags != 0)
             return fail(FCAMD_ERR_UNSUPPORTED, "the fused wrapper form takes no parent_rows / history_mask / stress2 / counters / flags");
         if (x->stress_prev != x->stress || (x->n_hist > 0 && x->history_prev != const_cast<const double* const*>(x->history)))
@@ -799,6 +858,8 @@ int fcamd_evaluate_batch(int count, fcamd_model* const* models, const int64_t* n
         if (!models[k]) return fail(FCAMD_ERR_BAD_ARG, "models[%d] is NULL", k);
         if (models[k]->ctx != c) return fail(FCAMD_ERR_BAD_ARG, "fcamd_evaluate_batch: models[%d] belongs to another context", k);
         if (args[k].wrapper_constraint != 0) return fail(FCAMD_ERR_UNSUPPORTED, "fcamd_evaluate_batch: the fused wrapper form is not batched (models[%d])", k);
+        if (has_fields(models[k], fields_of(&args[k])))
+            return fail(FCAMD_ERR_UNSUPPORTED, "fcamd_evaluate_batch: per-point parameter fields are not batched (models[%d]); use fcamd_evaluate_device_ex", k);
         const int st = check_device_ex(models[k], del_t, n[k], &args[k]);
         if (st != FCAMD_OK) return st;
     }

@@ -193,7 +193,12 @@ int enqueue(fcamd_model* m, double del_t, int64_t n, const double* grad, const d
             double* tangent, const double* const* hprev, double* const* hcur, hipStream_t stream, bool reset_counters,
             const int* rows = nullptr, unsigned long long* hmask = nullptr, int flags = 0, double* stress2 = nullptr,
             unsigned long long* counters = nullptr, const unsigned long long* emask_prev = nullptr,
-            unsigned long long* emask = nullptr);
+            unsigned long long* emask = nullptr, const double* const* fields = nullptr, int64_t field_p0 = 0);
+// per-point parameter fields (FCAMD_EVAL_PARAM_FIELDS): are there any, are they allowed for this model and form?
+// the field table of a call (FCAMD_EVAL_PARAM_FIELDS: it travels in stress_3d), or NULL
+const double* const* fields_of(const fcamd_eval_args* x);
+bool has_fields(const fcamd_model* m, const double* const* fields);
+int check_fields(const fcamd_model* m, const double* const* fields);
 
 // m->sc / m->tb brought up to date for `del_t` (what every launch does; the host tangent reads the tables before its launch)
 void constants_for_call(fcamd_model* m, double del_t);

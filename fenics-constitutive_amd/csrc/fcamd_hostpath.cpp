@@ -832,7 +832,7 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
     if (st != FCAMD_OK) return st;
     if (history_mask && !has_sparse_history(m->law))
         return fail(FCAMD_ERR_UNSUPPORTED, "sparse trial history exists for the plasticity laws only");
-    if (flags & ~(FCAMD_EVAL_SPARSE_TANGENT | FCAMD_EVAL_SPLIT_HISTORY | FCAMD_EVAL_PACKED_HISTORY))
+    if (flags & ~(FCAMD_EVAL_SPARSE_TANGENT | FCAMD_EVAL_SPLIT_HISTORY | FCAMD_EVAL_PACKED_HISTORY | FCAMD_EVAL_PARAM_FIELDS))
         return fail(FCAMD_ERR_UNSUPPORTED, "unknown FCAMD_EVAL_* flag in 0x%x (2, FCAMD_EVAL_DELTA_HISTORY of ABI 0.3, was removed in 0.4)", flags);
     if (packed && n > 0) {  // as fcamd_evaluate_device_ex
         if (!history_mask || !emask_prev || !emask || emask == emask_prev)
@@ -845,6 +845,9 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
     }
     if (!aligned16(stress) || !aligned16(stress_prev))
         return fail(FCAMD_ERR_ALIGN, "device arrays must be 16-byte aligned");
+    // per-point parameter fields (device arrays of n doubles): every launch below takes them at its first point
+    const double* const* fields = has_fields(m, fields_of(x)) ? fields_of(x) : nullptr;
+    if ((st = check_fields(m, fields)) != FCAMD_OK) return st;
     // history arrays of the state: the law's fields, or -- FCAMD_EVAL_SPLIT_HISTORY -- [scalar (n), eps_p rows (6 n)]
     const bool split = (flags & FCAMD_EVAL_SPLIT_HISTORY) != 0;
     const int NH = split ? 2 : m->info.n_hist;
@@ -872,6 +875,7 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
     // they are in the caller's array, and for the 3-D laws' one-launch pass only
     ExpandPool* pool = host_tangent_for(m, n, tangent_host);
     if ((flags & FCAMD_EVAL_SPARSE_TANGENT) || m->dims.gdim != 3) pool = nullptr;
+    if (fields) pool = nullptr;  // the host threads tile ONE tangent: with fields every point has its own, the kernel writes them
     const bool all_registered = mapped(c, grad, N * GD2 * sizeof(double)) &&
                                 (!stress_host || mapped(c, stress_host, N * SD * sizeof(double))) &&
                                 (pool || !tangent_host || mapped(c, tangent_host, N * TD * sizeof(double)));
@@ -915,7 +919,7 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
                          stress + SD * p0, tangent_host ? reinterpret_cast<double*>(c->bounce_dev + o_tan) : nullptr, hp, hc, s, false,
                          nullptr, history_mask ? reinterpret_cast<unsigned long long*>(history_mask) + p0 / 64 : nullptr,
                          flags & ~FCAMD_EVAL_SPARSE_TANGENT, second_store ? reinterpret_cast<double*>(c->bounce_dev + o_stress) : nullptr,
-                         nullptr, emask_prev ? emask_prev + p0 / 64 : nullptr, emask ? emask + p0 / 64 : nullptr);
+                         nullptr, emask_prev ? emask_prev + p0 / 64 : nullptr, emask ? emask + p0 / 64 : nullptr, fields, p0);
             if (st != FCAMD_OK) return drain_and_return(c, st);
             if (stress_host && !second_store)
                 HIP_TRY_DRAIN(c, hipMemcpyAsync(c->bounce + o_stress, stress + SD * p0, np * SD * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -958,7 +962,7 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
             return run_param_chunks(m, pool, n, tangent_host, stats, launch);
         }
         st = enqueue(m, del_t, n, z_grad, stress_prev, stress, z_tan, hist_prev, hist, s, false, nullptr,
-                     reinterpret_cast<unsigned long long*>(history_mask), flags, z_stress, nullptr, emask_prev, emask);
+                     reinterpret_cast<unsigned long long*>(history_mask), flags, z_stress, nullptr, emask_prev, emask, fields, 0);
         if (st != FCAMD_OK) return drain_and_return(c, st);
         return finish_single_stream(m, stats);
     }
@@ -992,7 +996,7 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
                      hp, hc, s, false, nullptr,
                      history_mask ? reinterpret_cast<unsigned long long*>(history_mask) + p0 / 64 : nullptr,
                      z_tan ? flags : (flags & ~FCAMD_EVAL_SPARSE_TANGENT),  // the staging buffer of a chunk holds no previous tangent: full rows
-                     nullptr, nullptr, emask_prev ? emask_prev + p0 / 64 : nullptr, emask ? emask + p0 / 64 : nullptr);
+                     nullptr, nullptr, emask_prev ? emask_prev + p0 / 64 : nullptr, emask ? emask + p0 / 64 : nullptr, fields, p0);
         if (st != FCAMD_OK) return drain_and_return(c, st);
         if (stress_host)
             HIP_TRY_DRAIN(c, hipMemcpyAsync(stress_host + SD * p0, stress + SD * p0, (size_t)np * SD * sizeof(double),

@@ -68,6 +68,19 @@ struct BatchEntry {
     int counts;        // the law counts (plastic points, Newton iterations, ...): args.counters is zeroed before the launch
     int pad[3];
 };
+// Per-point parameter fields (FCAMD_EVAL_PARAM_FIELDS): the second kernel parameter of evaluate_fields_kernel, never part of
+// EvalArgs.  f[k]: NULL (parameter k is the scalar v[k]) or the device array of parameter k, one double per point of the launch;
+// v[k]: the model's own parameter k (fcamd_model_create's order).  The kernels derive the law's constants per lane from these raw
+// values with the host's expressions (fill_constants), so a constant field gives the bits of the scalar law.
+struct FieldArgs {
+    const double* f[8];
+    double v[8];
+};
+static_assert(sizeof(EvalArgs) % alignof(FieldArgs) == 0, "FieldArgs follows EvalArgs in the kernarg segment");
+// the laws with field kernels: LinearElasticityModel (FULL), comfe LinearElasticity3D, VonMises3D, comfe MisesPlasticity3D
+inline bool law_has_field_kernels(int law) { return law == LAW_LE || law == LAW_VM3D || law == LAW_COMFE_LE || law == LAW_COMFE_MISES; }
+hipError_t launch_evaluate_fields(int law, const EvalArgs& args, const FieldArgs& fields, int grid, hipStream_t stream);
+
 int batch_variant_of(int law, const EvalArgs& args);
 // one table holds either Drucker-Prager laws (dp: the kernel cut for 3 waves per SIMD) or the others (4 waves): batch_law_is_dp
 bool batch_law_is_dp(int law);
@@ -83,6 +96,11 @@ typedef const EvalArgs FCAMD_CONSTANT& ArgsRef;
 typedef const Scalars FCAMD_CONSTANT& ScalarsRef;
 __device__ __forceinline__ ArgsRef kernel_args() {
     return *(const EvalArgs FCAMD_CONSTANT*)__builtin_amdgcn_kernarg_segment_ptr();
+}
+// the FieldArgs parameter of evaluate_fields_kernel / evaluate_fields_tail_kernel (right behind their EvalArgs)
+typedef const FieldArgs FCAMD_CONSTANT& FieldsRef;
+__device__ __forceinline__ FieldsRef field_args() {
+    return *(const FieldArgs FCAMD_CONSTANT*)((const char FCAMD_CONSTANT*)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(EvalArgs));
 }
 #endif
 

@@ -51,7 +51,8 @@ namespace fcamd {
 // ---------------------------------------------------------------------------------------
 // PM: the tangent leaves as 8 parameters per point (kFlagTangentParams: the host rebuilds the rows, fcamd_hosttangent.cpp) -- 0 never,
 // 1 always (the kernels instantiated for it), 2 decided by the flag at run time (the ragged last tile)
-template <int LAW, bool IDX, bool FULL, bool NT, int SPARSE = 0, int PM = 0, bool TWIN = false>
+// FIELDS: per-point parameters (evaluate_fields_kernel; LE, comfe LE, VonMises3D, comfe Mises)
+template <int LAW, bool IDX, bool FULL, bool NT, int SPARSE = 0, int PM = 0, bool TWIN = false, bool FIELDS = false>
 __device__ __forceinline__ void run_tile(ArgsRef a, const StressBases& sb, const Tables* T, double* region,
                                          int* rows_lds, long long p0, int npts, int lane, int r0,
                                          WaveStats& st) {
@@ -63,21 +64,21 @@ __device__ __forceinline__ void run_tile(ArgsRef a, const StressBases& sb, const
     asm volatile("" : "+v"(r0));
     lane &= kWave - 1;  // range known again: per-lane offsets are provably small and non-negative
     if constexpr (LAW == LAW_LE)
-        tile_linear_elasticity<IDX, FULL, NT>(a, sb, T, region, rows_lds, p0, npts, lane, r0);
+        tile_linear_elasticity<IDX, FULL, NT, FIELDS>(a, sb, T, region, rows_lds, p0, npts, lane, r0);
     else if constexpr (LAW == LAW_COMFE_LE)
-        tile_comfe_le<IDX, FULL, NT>(a, sb, T, region, rows_lds, p0, npts, lane, r0);
+        tile_comfe_le<IDX, FULL, NT, FIELDS>(a, sb, T, region, rows_lds, p0, npts, lane, r0);
     else if constexpr (LAW == LAW_MAXWELL)
         tile_sls<false, IDX, FULL, NT>(a, sb, T, region, rows_lds, p0, npts, lane, r0);
     else if constexpr (LAW == LAW_KELVIN)
         tile_sls<true, IDX, FULL, NT>(a, sb, T, region, rows_lds, p0, npts, lane, r0);
     else if constexpr (LAW == LAW_VM3D)
-        tile_von_mises<IDX, SPARSE, FULL, NT, PM, TWIN>(a, sb, T, region, rows_lds, p0, npts, lane, st);
+        tile_von_mises<IDX, SPARSE, FULL, NT, PM, TWIN, FIELDS>(a, sb, T, region, rows_lds, p0, npts, lane, st);
     else if constexpr (LAW == LAW_COMFE_DP)
         tile_comfe_dp<false, IDX, FULL, NT, PM>(a, sb, T, region, rows_lds, p0, npts, lane, r0, st);
     else if constexpr (LAW == LAW_COMFE_DP_HYPER)
         tile_comfe_dp<true, IDX, FULL, NT, PM>(a, sb, T, region, rows_lds, p0, npts, lane, r0, st);
     else
-        tile_comfe_mises<IDX, FULL, NT, PM>(a, sb, T, region, rows_lds, p0, npts, lane, st);
+        tile_comfe_mises<IDX, FULL, NT, PM, FIELDS>(a, sb, T, region, rows_lds, p0, npts, lane, st);
 }
 
 // One full tile of the main kernel.  Indexed kernel: when the 64 parent rows of the tile are
@@ -308,6 +309,44 @@ __global__ void __launch_bounds__(kWave) evaluate_tail_kernel(const EvalArgs) {
     __shared__ int rows_lds[kWave];
     stage_tables(a, &T);
     evaluate_tail_tile<LAW, IDX, SPARSE>(a, &T, region, rows_lds, (int)threadIdx.x);
+}
+
+// ---------------------------------------------------------------------------------------
+// Per-point parameter fields (FCAMD_EVAL_PARAM_FIELDS): the same tiles with every parameter of the law read per lane -- the
+// field's value of the lane's point, or the model's scalar -- and the law's constants derived from them in registers
+// (kernels/param_source.h).  A distinct kernel name and a second kernel parameter (FieldArgs, behind EvalArgs: field_args()), so
+// that nothing of evaluate_kernel changes.  Contiguous rows only (no parent_rows), no tangent-parameter or twin forms.
+// SPARSE (VonMises3D): as evaluate_kernel's; the comfe-rs Mises law takes its split / packed layouts from the flags at run time.
+// ---------------------------------------------------------------------------------------
+template <int LAW, int SPARSE>
+__global__ void __launch_bounds__(kBlock, 4) evaluate_fields_kernel(const EvalArgs, const FieldArgs) {
+    ArgsRef a = kernel_args();
+    __shared__ __attribute__((aligned(16))) Tables T;
+    __shared__ __attribute__((aligned(16))) double scratch[kWavesPerBlock][kRegionDoubles];
+    stage_tables(a, &T);
+    int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+    const long long nfull = a.n / kWave;
+    const long long wstride = (long long)gridDim.x * kWavesPerBlock;
+    const StressBases sb{a.stress_in, a.stress_out, a.tangent, a.stress_out2};
+    WaveStats st;
+    for (long long tile = (long long)blockIdx.x * kWavesPerBlock + wave; tile < nfull; tile += wstride)
+        run_tile<LAW, false, true, true, SPARSE, 0, false, true>(a, sb, &T, scratch[wave], nullptr, tile * kWave, kWave, lane, lane % 18, st);
+    flush_stats<LAW>(a, st, lane);
+}
+
+template <int LAW, int SPARSE>
+__global__ void __launch_bounds__(kWave) evaluate_fields_tail_kernel(const EvalArgs, const FieldArgs) {
+    ArgsRef a = kernel_args();
+    __shared__ __attribute__((aligned(16))) Tables T;
+    __shared__ __attribute__((aligned(16))) double region[kRegionDoubles];
+    stage_tables(a, &T);
+    const long long p0 = (a.n / kWave) * kWave;
+    const int lane = (int)threadIdx.x;
+    const StressBases sb{a.stress_in, a.stress_out, a.tangent, a.stress_out2};
+    WaveStats st;
+    run_tile<LAW, false, false, false, SPARSE, 0, false, true>(a, sb, &T, region, nullptr, p0, (int)(a.n - p0), lane, lane % 18, st);
+    flush_stats<LAW>(a, st, lane);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -549,6 +588,29 @@ hipError_t launch_evaluate_wrapped(int law, int wrap, const EvalArgs& args, int 
         case LAW_COMFE_MISES: return launch_wrapped_law<LAW_COMFE_MISES>(wrap, args, grid, stream);
         case LAW_COMFE_DP: return launch_wrapped_law<LAW_COMFE_DP>(wrap, args, grid, stream);
         case LAW_COMFE_DP_HYPER: return launch_wrapped_law<LAW_COMFE_DP_HYPER>(wrap, args, grid, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+template <int LAW, int SPARSE>
+static hipError_t launch_fields(const EvalArgs& args, const FieldArgs& f, int grid, hipStream_t stream) {
+    if (args.n >= kWave)
+        hipLaunchKernelGGL((evaluate_fields_kernel<LAW, SPARSE>), dim3(grid), dim3(kBlock), FCAMD_EXTRA_LDS, stream, args, f);
+    if (args.n % kWave != 0)
+        hipLaunchKernelGGL((evaluate_fields_tail_kernel<LAW, SPARSE>), dim3(1), dim3(kWave), 0, stream, args, f);
+    return hipGetLastError();
+}
+
+hipError_t launch_evaluate_fields(int law, const EvalArgs& args, const FieldArgs& f, int grid, hipStream_t stream) {
+    if (args.rows || (args.flags & (kFlagTangentParams | kFlagTwin))) return hipErrorInvalidValue;
+    switch (law) {
+        case LAW_LE: return launch_fields<LAW_LE, 0>(args, f, grid, stream);
+        case LAW_COMFE_LE: return launch_fields<LAW_COMFE_LE, 0>(args, f, grid, stream);
+        case LAW_COMFE_MISES: return launch_fields<LAW_COMFE_MISES, 0>(args, f, grid, stream);
+        case LAW_VM3D:
+            if (args.hmask && (args.flags & kFlagPackedHistory)) return launch_fields<LAW_VM3D, 2>(args, f, grid, stream);
+            if (args.hmask) return launch_fields<LAW_VM3D, 1>(args, f, grid, stream);
+            return launch_fields<LAW_VM3D, 0>(args, f, grid, stream);
         default: return hipErrorInvalidValue;
     }
 }

@@ -5,16 +5,19 @@
 #include "tangent_writers.h"
 #include "wrapped_io.h"
 #include "history_rows.h"
+#include "param_source.h"
 
 namespace fcamd {
 
 // comfe-rs MisesPlasticity3D (mises_plasticity.rs:58-126): the whole update of one point.  In: e, s (sigma_n),
 // h = [alpha, eps_p(6)].  Out: s (total stress), h (updated if plastic), tangent parameters B, sc2 and the
 // (non-unit) flow direction nv.  Returns whether the point is plastic.
-__device__ __forceinline__ bool cm_point(ScalarsRef sc, bool live, const double (&e)[6], double (&s)[6], double (&h)[7],
+// P: the parameter source (param_source.h) -- CMUniform, the launch's constants, or CMLane, the point's own
+template <class P>
+__device__ __forceinline__ bool cm_point(const P& p, bool live, const double (&e)[6], double (&s)[6], double (&h)[7],
                                          double& B, double& sc2, double (&nv)[6]) {
-    const double kappa = sc.s[2], y_0 = sc.s[3], hh = sc.s[4], two_mu = sc.s[5], den = sc.s[6], s32 = sc.s[7],
-                 three_mu = sc.s[8], hfac = sc.s[9];
+    const double kappa = p.kappa(), y_0 = p.y_0(), hh = p.h(), two_mu = p.two_mu(), den = p.den(), s32 = p.s32(),
+                 three_mu = p.three_mu(), hfac = p.hfac();
     const double alpha = h[0];
     // (p_0, s_0) = vol_dev(sigma) ; (tr, dev) = trace_dev(d_eps)
     const double p_0 = ((s[0] + s[1]) + s[2]) / 3.0;
@@ -66,12 +69,18 @@ __device__ __forceinline__ bool cm_point(ScalarsRef sc, bool live, const double 
     B = plastic ? two_mu * theta : two_mu;
     return plastic;
 }
+// the same on the launch's constants (the wrapper tiles)
+__device__ __forceinline__ bool cm_point(ScalarsRef sc, bool live, const double (&e)[6], double (&s)[6], double (&h)[7],
+                                         double& B, double& sc2, double (&nv)[6]) {
+    return cm_point(CMUniform{sc}, live, e, s, h, B, sc2, nv);
+}
 
 // --- comfe-rs MisesPlasticity3D: linear hardening, closed-form radial return ---------------
 // scalars: s[0]=strain factor (FRAC_1_SQRT_2), s[1]=mu, s[2]=kappa, s[3]=y_0, s[4]=h,
 //          s[5]=2*mu, s[6]=3*mu+h, s[7]=sqrt(3/2), s[8]=3*mu, s[9]=1/(1+h/(3 mu))
 // tables:  a = kappa*sym_id(x)sym_id, b = P_dev.   history field 0: [alpha, eps_p(6)] per point.
-template <bool IDX, bool FULL, bool NT, int PM = 0>
+// FIELDS: per-point parameters (evaluate_fields_kernel: field_args()); table a then holds sym_id(x)sym_id, scaled per point by its kappa
+template <bool IDX, bool FULL, bool NT, int PM = 0, bool FIELDS = false>
 __device__ __forceinline__ void tile_comfe_mises(ArgsRef a, const StressBases& sb, const Tables* T, double* region,
                                                  int* rows_lds, long long p0, int npts, int lane,
                                                  WaveStats& st) {
@@ -89,6 +98,7 @@ __device__ __forceinline__ void tile_comfe_mises(ArgsRef a, const StressBases& s
     else
         tile_load<7, FULL, NT>(ch, a.h0_in + p0 * 7, npts * 7, lane);
     const bool hist_in_place = (a.h0_in == a.h0_out);
+    const auto prm = cm_params<FIELDS>(a, p0, lane, live);
 
     double g[9], s[6], h[7], e[6];
     transpose_in<9>(cg, region, lane, g);
@@ -103,7 +113,7 @@ __device__ __forceinline__ void tile_comfe_mises(ArgsRef a, const StressBases& s
     mandel_strain(g, a.sc.s[0], e);
 
     double B, sc2, nv[6];
-    const bool plastic = cm_point(a.sc, live, e, s, h, B, sc2, nv);
+    const bool plastic = cm_point(prm, live, e, s, h, B, sc2, nv);
     const unsigned long long mask = __ballot(plastic);
     st.plastic += (lane == 0) ? (unsigned long long)__popcll(mask) : 0ull;
     const unsigned long long touched = sparse_touched(a, w, mask);
@@ -127,11 +137,12 @@ __device__ __forceinline__ void tile_comfe_mises(ArgsRef a, const StressBases& s
     const unsigned long long tneed = sparse_tangent_need<FULL>(a, touched);
     if (sb.tan && tneed != 0ull) {
         publish_tangent_params(region, lane, B, sc2, nv);
+        if constexpr (FIELDS) region[10 * lane + 8] = prm.kappa();
         wave_sync();
         if (tangent_params_mode<PM>(a))  // the host rebuilds the rows (fcamd_hosttangent.cpp)
             store_tangent_params<FULL, NT>(a, region, sb.tan, p0, npts, lane, mask);
         else
-            tangent_mises<true, IDX, FULL, NT>(region, T->a, T->b, sb.tan, p0, rows_lds, npts, lane, tneed, (a.flags & kFlagExactTangentRows) != 0);
+            tangent_mises<true, IDX, FULL, NT, FIELDS>(region, T->a, T->b, sb.tan, p0, rows_lds, npts, lane, tneed, (a.flags & kFlagExactTangentRows) != 0);
         wave_sync();
     }
 }

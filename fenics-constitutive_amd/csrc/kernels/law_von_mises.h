@@ -5,6 +5,7 @@
 #include "tangent_writers.h"
 #include "wrapped_io.h"
 #include "history_rows.h"
+#include "param_source.h"
 
 namespace fcamd {
 
@@ -20,9 +21,10 @@ struct VMTrial {
     double tr_eps, sigtrn, phitr;
 };
 
-__device__ __forceinline__ void vm_trial(ScalarsRef sc, const double (&e)[6], const double (&s)[6], double alpha_n,
-                                         VMTrial& t) {
-    const double two_mu = sc.s[2], s23 = sc.s[3], y0 = sc.s[4], dy = sc.s[5], mw = sc.s[6];
+// P: the parameter source (param_source.h) -- VMUniform, the launch's constants, or VMLane, the point's own
+template <class P>
+__device__ __forceinline__ void vm_trial(const P& p, const double (&e)[6], const double (&s)[6], double alpha_n, VMTrial& t) {
+    const double two_mu = p.two_mu(), s23 = p.s23(), y0 = p.y0(), dy = p.dy(), mw = p.mw();
     t.tr_eps = (e[0] + e[1]) + e[2];
     const double tr_sig = (s[0] + s[1]) + s[2];
     const double tr_eps3 = t.tr_eps / 3.0, tr_sig3 = tr_sig / 3.0;
@@ -47,8 +49,9 @@ struct VMReturn {
     double N[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 };
 
-__device__ __forceinline__ void vm_return(ScalarsRef sc, const VMTrial& t, double alpha_n, VMReturn& r, WaveStats& st) {
-    const double two_mu = sc.s[2], s23 = sc.s[3], y0 = sc.s[4], dy = sc.s[5], mw = sc.s[6], m2mu = sc.s[7], c23dyw = sc.s[8];
+template <class P>
+__device__ __forceinline__ void vm_return(const P& p, const VMTrial& t, double alpha_n, VMReturn& r, WaveStats& st) {
+    const double two_mu = p.two_mu(), s23 = p.s23(), y0 = p.y0(), dy = p.dy(), mw = p.mw(), m2mu = p.m2mu(), c23dyw = p.c23dyw();
     double g0 = 1.0, g1 = 0.0, xr = 1.0, xg;
     int it = 0;
     bool failed = false;
@@ -76,18 +79,33 @@ __device__ __forceinline__ void vm_return(ScalarsRef sc, const VMTrial& t, doubl
 }
 
 // stress (:165-167): sigma += (ka tr_eps) I2 + del_sigtr - (2 mu gamma) N;  tangent coefficients (:170-175)
-__device__ __forceinline__ void vm_stress(ScalarsRef sc, const VMTrial& t, const VMReturn& r, double (&s)[6]) {
-    const double kt = sc.s[1] * t.tr_eps, tmg = sc.s[2] * r.gamma;
+template <class P>
+__device__ __forceinline__ void vm_stress(const P& p, const VMTrial& t, const VMReturn& r, double (&s)[6]) {
+    const double kt = p.ka() * t.tr_eps, tmg = p.two_mu() * r.gamma;
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
         const double vol = i < 3 ? kt : kt * 0.0;
         s[i] = s[i] + ((vol + t.dsig[i]) - tmg * r.N[i]);
     }
 }
-__device__ __forceinline__ void vm_tangent_coefficients(ScalarsRef sc, const VMReturn& r, double& B, double& C) {
-    const double two_mu = sc.s[2], four_mu2 = sc.s[9];
+template <class P>
+__device__ __forceinline__ void vm_tangent_coefficients(const P& p, const VMReturn& r, double& B, double& C) {
+    const double two_mu = p.two_mu(), four_mu2 = p.four_mu2();
     B = two_mu * (1.0 - two_mu * r.xc2);
     C = four_mu2 * (r.xc2 - r.xc1);
+}
+// the same on the launch's constants (the wrapper tiles)
+__device__ __forceinline__ void vm_trial(ScalarsRef sc, const double (&e)[6], const double (&s)[6], double alpha_n, VMTrial& t) {
+    vm_trial(VMUniform{sc}, e, s, alpha_n, t);
+}
+__device__ __forceinline__ void vm_return(ScalarsRef sc, const VMTrial& t, double alpha_n, VMReturn& r, WaveStats& st) {
+    vm_return(VMUniform{sc}, t, alpha_n, r, st);
+}
+__device__ __forceinline__ void vm_stress(ScalarsRef sc, const VMTrial& t, const VMReturn& r, double (&s)[6]) {
+    vm_stress(VMUniform{sc}, t, r, s);
+}
+__device__ __forceinline__ void vm_tangent_coefficients(ScalarsRef sc, const VMReturn& r, double& B, double& C) {
+    vm_tangent_coefficients(VMUniform{sc}, r, B, C);
 }
 
 // --- VonMises3D: J2 plasticity, saturation hardening, scalar Newton per point -----------------
@@ -98,7 +116,8 @@ __device__ __forceinline__ void vm_tangent_coefficients(ScalarsRef sc, const VMR
 //       2 = sparse protocol on the packed plastic-strain layout (history_rows.h: PackedRows)
 // PM: the tangent leaves as its 8 parameters per point (0 never, 1 always, 2 by kFlagTangentParams at run time; fcamd_kernels.hip: run_tile)
 // TWIN: the synthetic twin (tangent_writers.h: kFlagTwin) -- ballots from a.cache3d, no constitutive arithmetic
-template <bool IDX, int HIST, bool FULL, bool NT, int PM = 0, bool TWIN = false>
+// FIELDS: per-point parameters (evaluate_fields_kernel: field_args()); table a then holds xioi, scaled per point by its ka
+template <bool IDX, int HIST, bool FULL, bool NT, int PM = 0, bool TWIN = false, bool FIELDS = false>
 __device__ __forceinline__ void tile_von_mises(ArgsRef a, const StressBases& sb, const Tables* T, double* region,
                                                int* rows_lds, long long p0, int npts, int lane,
                                                WaveStats& st) {
@@ -120,6 +139,7 @@ __device__ __forceinline__ void tile_von_mises(ArgsRef a, const StressBases& sb,
     sr.load(a, sb, p0, npts, lane, rows_lds);
     const bool live = FULL || lane < npts;
     const double alpha_n = live ? a.h1_in[p0 + lane] : 0.0;
+    const auto prm = vm_params<FIELDS>(a, p0, lane, live);
     const bool hist_in_place = (a.h0_in == a.h0_out) && (a.h1_in == a.h1_out);
     // packed layout: a tile that was plastic at the previous evaluate is touched whatever happens now (new values or stale
     // rows) -- its committed run is requested right away, long before the ballot
@@ -145,7 +165,7 @@ __device__ __forceinline__ void tile_von_mises(ArgsRef a, const StressBases& sb,
         tr.tr_eps = e[0], tr.sigtrn = 1.0, tr.phitr = 0.0;
         plastic = live && ((recorded >> lane) & 1ull) != 0ull;
     } else {
-        vm_trial(a.sc, e, s, alpha_n, tr);
+        vm_trial(prm, e, s, alpha_n, tr);
         plastic = live && (tr.phitr > 0.0);
     }
     const unsigned long long mask = __ballot(plastic);
@@ -209,7 +229,7 @@ __device__ __forceinline__ void tile_von_mises(ArgsRef a, const StressBases& sb,
                 for (int i = 0; i < 6; ++i) rm.N[i] = s[i];
             }
         } else {
-            if (plastic) vm_return(a.sc, tr, alpha_n, rm, st);
+            if (plastic) vm_return(prm, tr, alpha_n, rm, st);
         }
         st.plastic += (lane == 0) ? (unsigned long long)__popcll(mask) : 0ull;
     }
@@ -225,7 +245,7 @@ __device__ __forceinline__ void tile_von_mises(ArgsRef a, const StressBases& sb,
         if (ep_in_lanes) transpose_in<6>(ce, region, lane, ep);
     }
 
-    vm_stress(a.sc, tr, rm, s);
+    vm_stress(prm, tr, rm, s);
     sr.put(sb, region, lane, s, p0, npts, rows_lds);
 
     // history: eps_n += gamma N ; alpha += sqrt(2/3) gamma
@@ -270,8 +290,9 @@ __device__ __forceinline__ void tile_von_mises(ArgsRef a, const StressBases& sb,
     const unsigned long long tneed = sparse_tangent_need<FULL>(a, need_mask);
     if (sb.tan && tneed != 0ull) {
         double B, C;
-        vm_tangent_coefficients(a.sc, rm, B, C);
+        vm_tangent_coefficients(prm, rm, B, C);
         publish_tangent_params(region, lane, B, C, rm.N);
+        if constexpr (FIELDS) region[10 * lane + 8] = prm.ka();
         wave_sync();
         if constexpr (TWIN && FULL && !IDX) {
             if (tneed == ~0ull) tangent_const<false, true, NT>(T->a, sb.tan, p0, rows_lds, npts, lane, lane % 18);
@@ -279,7 +300,7 @@ __device__ __forceinline__ void tile_von_mises(ArgsRef a, const StressBases& sb,
         } else if (tangent_params_mode<PM>(a))  // the host rebuilds the rows (fcamd_hosttangent.cpp)
             store_tangent_params<FULL, NT>(a, region, sb.tan, p0, npts, lane, mask);
         else
-            tangent_mises<false, IDX, FULL, NT>(region, T->a, T->b, sb.tan, p0, rows_lds, npts, lane, tneed, (a.flags & kFlagExactTangentRows) != 0);
+            tangent_mises<false, IDX, FULL, NT, FIELDS>(region, T->a, T->b, sb.tan, p0, rows_lds, npts, lane, tneed, (a.flags & kFlagExactTangentRows) != 0);
         wave_sync();
     }
 }

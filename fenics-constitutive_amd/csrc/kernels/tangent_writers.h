@@ -143,13 +143,20 @@ __device__ __forceinline__ ChunkMap chunk_map(const ChunkLane& c) {
 //                                               mises_plasticity.rs:118-123)
 // `tneed`: the points of the tile whose tangent rows are written (all ones unless the caller runs the
 // sparse-tangent protocol, see sparse_tangent_need()).
-template <bool COMFE>
+// FIELDS (per-point parameters): ta holds xioi resp. sym_id(x)sym_id and lane p has published its ka resp. kappa at tp[10p + 8] --
+// the entry is that product, the host's table expression (fill_constants), per point.
+template <bool COMFE, bool FIELDS = false>
 __device__ __forceinline__ d2 tangent_mises_chunk(const double* tp, const double* ta, const double* tb, int p, int r, int i, int jj) {
     const double* t = tp + 10 * p;
     const d2 bc = reinterpret_cast<const d2*>(t)[0];
     const double ni = t[2 + i];
     const d2 nj = *reinterpret_cast<const d2*>(t + 2 + 2 * jj);
-    const d2 a = *reinterpret_cast<const d2*>(ta + 2 * r);  // 6 i + j = 2 r
+    d2 a = *reinterpret_cast<const d2*>(ta + 2 * r);  // 6 i + j = 2 r
+    if constexpr (FIELDS) {
+        const double k = t[8];
+        a.x = k * a.x;
+        a.y = k * a.y;
+    }
     const d2 b = *reinterpret_cast<const d2*>(tb + 2 * r);
     d2 v;
     if constexpr (COMFE) {
@@ -162,7 +169,7 @@ __device__ __forceinline__ d2 tangent_mises_chunk(const double* tp, const double
     return v;
 }
 
-template <bool COMFE, bool NT, bool MASKED, int K>
+template <bool COMFE, bool NT, bool MASKED, int K, bool FIELDS>
 __device__ __forceinline__ void tangent_mises_pass(const double* tp, const double* ta, const double* tb, double* tile, int lane,
                                                    const ChunkLane& cl, unsigned long long tneed, bool exact_rows) {
     const ChunkMap m = chunk_map<K>(cl);
@@ -170,16 +177,16 @@ __device__ __forceinline__ void tangent_mises_pass(const double* tp, const doubl
     if constexpr (MASKED) wanted = tangent_chunk_wanted(tneed, m.p, exact_rows);
     // destination: the pass's base (scalar) + this lane's byte offset (32 bits, the same in every pass)
     char* dst = reinterpret_cast<char*>(tile) + K * (kWave * 16) + (unsigned)lane * 16u;
-    if (wanted) store_tangent16<NT>(reinterpret_cast<double*>(dst), tangent_mises_chunk<COMFE>(tp, ta, tb, m.p, m.r, m.i, m.jj));
+    if (wanted) store_tangent16<NT>(reinterpret_cast<double*>(dst), tangent_mises_chunk<COMFE, FIELDS>(tp, ta, tb, m.p, m.r, m.i, m.jj));
     // bound the register pressure: let the scheduler interleave at most 3 chunks
     if constexpr (K % kTangentGroup == kTangentGroup - 1) __builtin_amdgcn_sched_barrier(0);
 }
 
-template <bool COMFE, bool NT, bool MASKED, int... K>
+template <bool COMFE, bool NT, bool MASKED, bool FIELDS, int... K>
 __device__ __forceinline__ void tangent_mises_passes(const double* tp, const double* ta, const double* tb, double* tile, int lane,
                                                      unsigned long long tneed, bool exact_rows, std::integer_sequence<int, K...>) {
     const ChunkLane cl = chunk_lane(lane);
-    (tangent_mises_pass<COMFE, NT, MASKED, K>(tp, ta, tb, tile, lane, cl, tneed, exact_rows), ...);
+    (tangent_mises_pass<COMFE, NT, MASKED, K, FIELDS>(tp, ta, tb, tile, lane, cl, tneed, exact_rows), ...);
 }
 
 // The request stream of the masked passes without their arithmetic (the synthetic twin of the sparse-tangent iteration, law_von_mises.h:
@@ -199,16 +206,16 @@ __device__ __forceinline__ void tangent_twin_passes(const double* tp, double* ti
     (tangent_twin_pass<NT, K>(tp, tile, lane, cl, tneed, exact_rows), ...);
 }
 
-template <bool COMFE, bool IDX, bool FULL, bool NT>
+template <bool COMFE, bool IDX, bool FULL, bool NT, bool FIELDS = false>
 __device__ __forceinline__ void tangent_mises(const double* tp, const double* ta, const double* tb,
                                               double* tangent, long long p0, const int* rows_lds,
                                               int npts, int lane, unsigned long long tneed, bool exact_rows = false) {
     if constexpr (FULL && !IDX) {  // the contiguous tile: incremental chunk maps; the need test only under the sparse-tangent protocol
         double* tile = tangent + p0 * 36;
         if (tneed == ~0ull)
-            tangent_mises_passes<COMFE, NT, false>(tp, ta, tb, tile, lane, tneed, false, std::make_integer_sequence<int, 18>{});
+            tangent_mises_passes<COMFE, NT, false, FIELDS>(tp, ta, tb, tile, lane, tneed, false, std::make_integer_sequence<int, 18>{});
         else
-            tangent_mises_passes<COMFE, NT, true>(tp, ta, tb, tile, lane, tneed, exact_rows, std::make_integer_sequence<int, 18>{});
+            tangent_mises_passes<COMFE, NT, true, FIELDS>(tp, ta, tb, tile, lane, tneed, exact_rows, std::make_integer_sequence<int, 18>{});
         return;
     }
     const int nchunks = npts * 18;
@@ -218,10 +225,30 @@ __device__ __forceinline__ void tangent_mises(const double* tp, const double* ta
         const int p = q / 18;
         const int r = q - 18 * p;
         const int i = r / 3;
-        const d2 v = tangent_mises_chunk<COMFE>(tp, ta, tb, p, r, i, r - 3 * i);
+        const d2 v = tangent_mises_chunk<COMFE, FIELDS>(tp, ta, tb, p, r, i, r - 3 * i);
         if ((FULL || q < nchunks) && ((tneed >> p) & 1ull)) store_tangent16<NT>(tangent_chunk<IDX>(tangent, p0, q, rows_lds), v);
         // bound the register pressure: let the scheduler interleave at most 3 chunks
         if (k % kTangentGroup == kTangentGroup - 1) __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// Per-point elastic tangent (the linear-elastic laws with parameter fields): lane p has published the four distinct entries of its
+// matrix at tp[10p + 0..3] (param_source.h: elastic_entry); every lane builds and stores the 18 chunks of its passes.
+template <bool FULL, bool NT>
+__device__ __forceinline__ void tangent_elastic_points(const double* tp, double* tangent, long long p0, int npts, int lane) {
+    const int nchunks = npts * 18;
+#pragma unroll
+    for (int k = 0; k < 18; ++k) {
+        const int q = k * kWave + lane;
+        const int p = q / 18;
+        const int r = q - 18 * p;
+        const int i = r / 3;
+        const int j = 2 * (r - 3 * i);
+        const double* t = tp + 10 * p;
+        d2 v;
+        v.x = (i < 3 && j < 3) ? (i == j ? t[0] : t[1]) : (i == j ? t[2] : t[3]);
+        v.y = (i < 3 && j + 1 < 3) ? (i == j + 1 ? t[0] : t[1]) : (i == j + 1 ? t[2] : t[3]);
+        if (FULL || q < nchunks) store_tangent16<NT>(tangent + p0 * 36 + 2 * q, v);
     }
 }
 

@@ -142,6 +142,31 @@ def _warn_small_call(law, n: int) -> None:
                   "Shown once per law; FCAMD_SMALL_CALL_WARNING=0 silences it.", RuntimeWarning, stacklevel=3)
 
 
+def parameter_field(name: str, value):
+    """A per-point parameter field, or None: a 1-D float64 NumPy array or ROCm tensor with MORE than one element is a field
+    over ``len(value)`` points and comes back as a host copy (values are taken at construction, as scalars are); anything
+    else -- scalars, one-element arrays -- keeps its scalar meaning.  A many-element value of another dtype or shape raises."""
+    if _is_torch(value):
+        import torch
+
+        if value.numel() <= 1:
+            return None
+        if value.dim() != 1:
+            raise ValueError(f"parameter field '{name}' must be 1-D, got shape {tuple(value.shape)}")
+        if value.dtype != torch.float64:
+            raise TypeError(f"parameter field '{name}' must be float64, got {value.dtype}")
+        return value.detach().cpu().numpy().copy()
+    if isinstance(value, np.ndarray):
+        if value.size <= 1:
+            return None
+        if value.ndim != 1:
+            raise ValueError(f"parameter field '{name}' must be 1-D, got shape {value.shape}")
+        if value.dtype != np.float64:
+            raise TypeError(f"parameter field '{name}' must be float64, got {value.dtype}")
+        return np.array(value, dtype=np.float64, copy=True)
+    return None
+
+
 class DeviceLaw(IncrSmallStrainModel):
     """Base of all GPU-backed laws: owns the C model handle (created lazily, per device)
     and implements ``evaluate`` on top of the C ABI with the reference's validation."""
@@ -155,10 +180,37 @@ class DeviceLaw(IncrSmallStrainModel):
     #: keeps a reference to every pinned array until ``unpin_arrays()``: page-locked memory must not
     #: be freed while registered (a later array at the same address would DMA through stale pages).
     auto_pin = False
+    #: the laws whose kernels take per-point parameter fields (fcamd_eval_args.param_fields; FULL constraint)
+    _supports_fields = False
+    #: names of the parameters in fcamd_model_create's order (the field error messages, ``field_names``)
+    _parameter_names: tuple = ()
 
     def __init__(self, parameter_vector, constraint: StressStrainConstraint = None):
         self._constraint = constraint if constraint is not None else StressStrainConstraint.FULL
-        self._parameter_vector = [float(p) for p in parameter_vector]
+        names = self._parameter_names or tuple(str(k) for k in range(len(parameter_vector)))
+        # per-point parameter fields: {parameter index: host copy}; the model's own parameter k is then the field's first value
+        # (the kernels read it for no point; it keeps the handle's host constants finite)
+        self._fields = {}
+        for k, p in enumerate(parameter_vector):
+            try:
+                f = parameter_field(names[k], p)
+            except (TypeError, ValueError):
+                if self._supports_fields:
+                    raise
+                f = None  # a law without field kernels refuses it as it always did (float() below)
+            if f is not None:
+                self._fields[k] = f
+        if self._fields:
+            if not self._supports_fields or (self._constraint != StressStrainConstraint.FULL):
+                raise NotImplementedError(f"{type(self).__name__} ({self._constraint.name}): per-point parameter fields exist for "
+                                          "LinearElasticityModel (FULL), LinearElasticity3D, VonMises3D and "
+                                          "MisesPlasticityLinearHardening3D")
+            lengths = {len(f) for f in self._fields.values()}
+            if len(lengths) != 1:
+                raise ValueError(f"all parameter fields of a law have the same length, got {sorted(lengths)}")
+        self._parameter_vector = [float(self._fields[k][0]) if k in self._fields else float(p) for k, p in enumerate(parameter_vector)]
+        self._field_names = tuple(names[k] for k in sorted(self._fields))
+        self._field_dev = {}  # device ordinal -> the fields' device copies (uploaded on first use)
         # C model handles, one per (thread, device), in thread-local storage: they are destroyed -- and with
         # the last of them the thread's context -- when the thread that created them ends
         self._tls = threading.local()
@@ -174,6 +226,37 @@ class DeviceLaw(IncrSmallStrainModel):
     @property
     def constraint(self) -> StressStrainConstraint:
         return self._constraint
+
+    # -- per-point parameter fields ------------------------------------------------------------
+    @property
+    def field_points(self):
+        """number of points of the law's parameter fields (``None``: no fields, every parameter is a scalar)"""
+        return len(next(iter(self._fields.values()))) if self._fields else None
+
+    @property
+    def field_names(self) -> tuple:
+        """the parameters given per point"""
+        return self._field_names
+
+    def _field_ptrs(self, device: int, n: int):
+        """``fcamd_eval_args.param_fields`` of a call over ``n`` points on ``device``: one device address per parameter (0 = the
+        scalar), or None without fields.  The fields are uploaded once per device."""
+        if not self._fields:
+            return None
+        if n != self.field_points:
+            raise AssertionError(f"{type(self).__name__}: the parameter fields have {self.field_points} points, the call has {n}")
+        dev = self._field_dev.get(device)
+        if dev is None:
+            import torch
+
+            from .hostio import to_device
+
+            dev = self._field_dev[device] = {k: to_device(f, torch.device("cuda", device)) for k, f in self._fields.items()}
+        return [dev[k].data_ptr() if k in dev else 0 for k in range(len(self._parameter_vector))]
+
+    def _refuse_fields(self, what: str) -> None:
+        if self._fields:
+            raise NotImplementedError(f"{type(self).__name__}: {what} does not support per-point parameter fields")
 
     # -- C handle ---------------------------------------------------------------------------
     def _handle(self, device: int = 0) -> _capi.Model:
@@ -195,6 +278,8 @@ class DeviceLaw(IncrSmallStrainModel):
         of a dolfinx process that drives a whole node; results are bit-identical to one device.  The environment
         variable ``FCAMD_DEVICES`` ("0,1,2,3" / "all") sets the default for every law.  Returns ``self``."""
         devices = None if devices is None else [int(d) for d in devices]
+        if devices is not None:
+            self._refuse_fields("use_devices")
         if devices != self._devices:
             self.unpin_arrays()
             if self._multi_handle is not None:
@@ -262,6 +347,9 @@ class DeviceLaw(IncrSmallStrainModel):
             _check_numpy("tangent", tangent)
         for (name, _), h in zip(self._history_fields(), hist):
             _check_numpy(f"history['{name}']", h)
+        if self._fields:
+            self._evaluate_host_fields(t, del_t, n, grad, stress, tangent, hist)
+            return
         multi = self._devices is not None
         m = self._multi() if multi else self._handle(_capi.default_device())
         if self.auto_pin:
@@ -270,6 +358,30 @@ class DeviceLaw(IncrSmallStrainModel):
             t, del_t, n, grad.ctypes.data, stress.ctypes.data,
             None if tangent is None else tangent.ctypes.data, [h.ctypes.data for h in hist],
         )
+
+    def _evaluate_host_fields(self, t, del_t, n, grad, stress, tangent, hist) -> None:
+        """the ndarray call of a law with parameter fields: through device copies of the arrays (the host entry takes no
+        argument struct), the device kernels, and back in place; non-convergence raises after the results are written, as
+        the host entry does"""
+        import torch
+
+        from .hostio import assign, to_device
+
+        if self._devices is not None:
+            self._refuse_fields("use_devices")
+        dev = _capi.default_device()
+        self._field_ptrs(dev, n)  # the size check before anything moves
+        d = torch.device("cuda", dev)
+        arrays = [grad, stress] + ([] if tangent is None else [tangent]) + list(hist)
+        on_dev = [to_device(a.reshape(-1), d) for a in arrays]
+        g, s = on_dev[0], on_dev[1]
+        tan = on_dev[2] if tangent is not None else None
+        h = on_dev[3 if tangent is not None else 2:]
+        with torch.cuda.device(d):
+            self._evaluate_device(t, del_t, n, g, s, tan, h)
+        for a, x in zip(arrays[1:], on_dev[1:]):
+            assign(a.reshape(-1), x)  # (ordered after the launch: torch's current stream)
+        self.device_stats(dev)
 
     def _pin(self, ctx, arrays) -> None:
         pinned = self.__dict__.setdefault("_pinned", {})  # (ptr, nbytes) -> (array kept alive, its context) | None
@@ -319,12 +431,20 @@ class DeviceLaw(IncrSmallStrainModel):
             _check_torch(f"history['{name}']", h)
         dev = grad.device.index or 0
         m = self._handle(dev)
+        fields = self._field_ptrs(dev, n)
         m.ctx.set_stream(_current_stream_ptr(dev))
+        hp = None if hist_prev is None else [_check_torch("history_prev", h).data_ptr() for h in hist_prev]
+        if fields is not None:
+            m.evaluate_device_ex(t, del_t, n, grad.data_ptr(), stress.data_ptr() if stress_prev is None else
+                                 _check_torch("stress_prev", stress_prev).data_ptr(), stress.data_ptr(),
+                                 None if tangent is None else tangent.data_ptr(), [h.data_ptr() for h in hist] if hp is None else hp,
+                                 [h.data_ptr() for h in hist], field_ptrs=fields)
+            return
         m.evaluate_device(
             t, del_t, n, grad.data_ptr(), stress.data_ptr(),
             None if tangent is None else tangent.data_ptr(), [h.data_ptr() for h in hist],
             None if stress_prev is None else _check_torch("stress_prev", stress_prev).data_ptr(),
-            None if hist_prev is None else [_check_torch("history_prev", h).data_ptr() for h in hist_prev],
+            hp,
         )
 
     def evaluate_from(self, t, del_t, grad_del_u, stress_prev, stress, tangent, history_prev, history,
@@ -364,8 +484,9 @@ class DeviceLaw(IncrSmallStrainModel):
             _check_torch("array", x)
         dev = grad_del_u.device.index or 0
         m = self._handle(dev)
+        fields = self._field_ptrs(dev, n)
         m.ctx.set_stream(_current_stream_ptr(dev))
-        if (sparse_tangent and tangent is not None) or counters is not None or split_history or packed_masks is not None:
+        if (sparse_tangent and tangent is not None) or counters is not None or split_history or packed_masks is not None or fields:
             flags = _capi.EVAL_SPARSE_TANGENT if (sparse_tangent and tangent is not None and history_mask is not None) else 0
             pm = None
             if packed_masks is not None:
@@ -381,7 +502,7 @@ class DeviceLaw(IncrSmallStrainModel):
                 None if tangent is None else _check_torch("tangent", tangent).data_ptr(),
                 [h.data_ptr() for h in hprev], [h.data_ptr() for h in hist],
                 None, None if history_mask is None else history_mask.data_ptr(), flags,
-                counters_ptr=_counters_ptr(counters), packed_mask_ptrs=pm)
+                counters_ptr=_counters_ptr(counters), packed_mask_ptrs=pm, field_ptrs=fields)
             return
         m.evaluate_device_from_sparse(
             t, del_t, n, grad_del_u.data_ptr(), stress_prev.data_ptr(), stress.data_ptr(),
@@ -397,6 +518,8 @@ class DeviceLaw(IncrSmallStrainModel):
         ``grad_del_u`` and the history are local to the law.  Replaces map_to_sub + evaluate +
         map_to_parent of ``LawOnSubMesh`` (solver/_lawonsubmesh.py:58-95) by one launch."""
         import torch
+
+        self._refuse_fields("evaluate_indexed (parent_rows)")
 
         hist = self._history_arrays(history)
         hprev = hist if history_prev is None else self._history_arrays(history_prev)

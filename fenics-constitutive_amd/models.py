@@ -12,6 +12,10 @@ Reference classes mirrored:
   SpringKelvinModel                  models/spring_kelvin_model.py:9-102
   LinearElasticity3D                 models/rust_models.py:84-94  (comfe-rs linear_elasticity.rs)
   MisesPlasticityLinearHardening3D   models/rust_models.py:145-161 (comfe-rs mises_plasticity.rs)
+
+Per-point parameters (LinearElasticityModel under FULL, LinearElasticity3D, VonMises3D, MisesPlasticityLinearHardening3D):
+any parameter may be a 1-D float64 array (or ROCm tensor) with more than one element -- a field over that many quadrature
+points (``field_points``); the other parameters keep their scalar meaning.  See ``device.parameter_field``.
 """
 
 from __future__ import annotations
@@ -19,7 +23,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _capi
-from .device import DeviceLaw
+from .device import DeviceLaw, parameter_field
 from .interfaces import StressStrainConstraint
 from .utils import get_elastic_tangent, get_identity, lame_parameters
 
@@ -44,11 +48,19 @@ class LinearElasticityModel(DeviceLaw):
     """
 
     _model_id = _capi.LINEAR_ELASTICITY
+    _supports_fields = True
+    _parameter_names = ("E", "nu")
 
     def __init__(self, parameters: dict[str, float], constraint: StressStrainConstraint):
         E, nu = parameters["E"], parameters["nu"]
         super().__init__([E, nu], constraint)
-        self.D = get_elastic_tangent(E, nu, constraint)
+        if self.field_points is None:
+            self.D = get_elastic_tangent(E, nu, constraint)
+        else:  # one D per point, built by the kernels; refused where the scalar law refuses (lame_parameters' divisions)
+            nu_f = np.asarray(self._fields.get(1, self._parameter_vector[1]), dtype=np.float64)
+            if np.any(2.0 * (1.0 + nu_f) == 0.0) or np.any((1.0 + nu_f) * (1.0 - 2.0 * nu_f) == 0.0):
+                raise ZeroDivisionError("float division by zero")
+            self.D = None
 
     @property
     def history_dim(self) -> None:
@@ -65,6 +77,8 @@ class VonMises3D(DeviceLaw):
     """
 
     _model_id = _capi.VON_MISES_3D
+    _supports_fields = True
+    _parameter_names = ("p_ka", "p_mu", "p_y0", "p_y00", "p_w")
 
     def __init__(self, param: dict[str, float]):
         self.p_ka = param["p_ka"]
@@ -140,10 +154,22 @@ class SpringKelvinModel(_SpringBase):
 
 def _scalar(parameters: dict, key: str) -> float:
     """Rust-style parameter dicts carry one-element arrays (tests/models/test_plasticity.py:26-31)."""
+    try:
+        field = parameter_field(key, parameters[key]) is not None
+    except (TypeError, ValueError):
+        field = False  # not a well-formed field: refused below as before
+    if field:
+        raise NotImplementedError(f"parameter '{key}': this law takes no per-point parameter fields")
     v = np.asarray(parameters[key], dtype=np.float64).reshape(-1)
     if v.size != 1:
         raise ValueError(f"parameter '{key}' must have exactly one entry")
     return float(v[0])
+
+
+def _scalar_or_field(parameters: dict, key: str):
+    """``_scalar``, or the value itself when it is a per-point field (``device.parameter_field``; the laws with field kernels)"""
+    v = parameters[key]
+    return v if parameter_field(key, v) is not None else _scalar(parameters, key)
 
 
 class LinearElasticity3D(DeviceLaw):
@@ -154,9 +180,11 @@ class LinearElasticity3D(DeviceLaw):
     """
 
     _model_id = _capi.COMFE_LINEAR_ELASTICITY
+    _supports_fields = True
+    _parameter_names = ("mu", "kappa")
 
     def __init__(self, parameters: dict[str, np.ndarray]):
-        super().__init__([_scalar(parameters, "mu"), _scalar(parameters, "kappa")], StressStrainConstraint.FULL)
+        super().__init__([_scalar_or_field(parameters, "mu"), _scalar_or_field(parameters, "kappa")], StressStrainConstraint.FULL)
 
     @property
     def history_dim(self) -> None:
@@ -172,10 +200,12 @@ class MisesPlasticityLinearHardening3D(DeviceLaw):
     """
 
     _model_id = _capi.COMFE_MISES_PLASTICITY
+    _supports_fields = True
+    _parameter_names = ("mu", "kappa", "y_0", "h")
 
     def __init__(self, parameters: dict[str, np.ndarray]):
         super().__init__(
-            [_scalar(parameters, k) for k in ("mu", "kappa", "y_0", "h")], StressStrainConstraint.FULL
+            [_scalar_or_field(parameters, k) for k in self._parameter_names], StressStrainConstraint.FULL
         )
 
     @property

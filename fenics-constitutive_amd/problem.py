@@ -127,6 +127,9 @@ class ResidentProblemState:
         self._f = f
         if isinstance(laws, DeviceLaw):
             laws = [(laws, None)]
+        for law, _ in laws:
+            if law.field_points is not None:
+                raise NotImplementedError("ResidentProblemState: laws with per-point parameter fields are not supported (use ResidentState)")
         self._laws = []
         covered = np.zeros(self.n, dtype=np.int64)
         for law, rows in laws:

@@ -68,6 +68,8 @@ class ResidentState:
         # ``history_committed`` assemble the reference's rows on demand (copies -- initialise with ``set_state``).
 
         self.law, self.n = law, int(n)
+        if law.field_points is not None and law.field_points != self.n:
+            raise AssertionError(f"{type(law).__name__}: the parameter fields have {law.field_points} points, the state has {self.n}")
         from . import _capi
         from .device import SPLIT_HISTORY_FIELDS, SPLIT_HISTORY_LAWS
 
@@ -299,7 +301,10 @@ class ResidentState:
         # ragged tile: 52 -> 38 us per iteration at 1e4 points)
         sig = (float(del_t), g.data_ptr(), 0 if tangent is None else tangent.data_ptr(), sparse, self.stress_committed.data_ptr(),
                self.stress.data_ptr(), self.generation)
-        self._launch_cache.run(self._c, sig, lambda: self._launch(t, del_t, g, tangent, sparse), _current_stream_ptr(self.device.index or 0))
+        if self.law.field_points is not None:  # parameter fields are not batched: the law's own launch, every time
+            self._launch(t, del_t, g, tangent, sparse)
+        else:
+            self._launch_cache.run(self._c, sig, lambda: self._launch(t, del_t, g, tangent, sparse), _current_stream_ptr(self.device.index or 0))
         self._tangent_key = key
         self._tangent_target = "dev"
         self._evaluated = True
@@ -482,7 +487,8 @@ class ResidentState:
                 t, del_t, self.n, grad_del_u.ctypes.data, self.stress_committed.data_ptr(), self.stress.data_ptr(),
                 hp, hc, None if self._mask is None else self._mask.data_ptr(),
                 None if stress is None else stress.ctypes.data, None if tangent is None else tangent.ctypes.data, flags,
-                packed_mask_ptrs=(self._ever[self._c].data_ptr(), self._ever[1 - self._c].data_ptr()) if self._packed else None)
+                packed_mask_ptrs=(self._ever[self._c].data_ptr(), self._ever[1 - self._c].data_ptr()) if self._packed else None,
+                field_ptrs=self.law._field_ptrs(dev, self.n))
         except Exception as e:
             self._failed = e  # the trial state is not fit to be committed: update() raises until a clean evaluate
             raise

@@ -75,6 +75,9 @@ class ShardedEvaluator:
     def __init__(self, law, n_global: int, group=None):
         import torch.distributed as dist
 
+        if getattr(law, "field_points", None) is not None:
+            raise NotImplementedError("ShardedEvaluator: laws with per-point parameter fields are not supported")
+
         self.law = law
         self.group = group
         self.dist = dist

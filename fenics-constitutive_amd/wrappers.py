@@ -41,6 +41,8 @@ class _From3D(IncrSmallStrainModel):
 
     def __init__(self, model: IncrSmallStrainModel) -> None:
         assert model.constraint.name == "FULL"
+        if getattr(model, "field_points", None) is not None:
+            raise NotImplementedError(f"{type(self).__name__}: laws with per-point parameter fields are not supported")
         self.model = model
         self.stress_3d = None
         self.tangent_3d = None

@@ -21,6 +21,7 @@
  *
  * Plain pointers and sizes only; nothing from torch or numpy appears here.
  *
+ * Version 0.5: FCAMD_EVAL_PARAM_FIELDS, per-point material parameters, with the entries and the argument struct of 0.4.
  * Version 0.4 (round 4): the boundary is THREE evaluate entries -- fcamd_evaluate_host (the ndarray call),
  * fcamd_evaluate_device_ex (device arrays, every option in one argument struct), fcamd_evaluate_resident (host
  * assembler on a device-resident state) --, plus (round 5) fcamd_evaluate_batch, the laws of one form() in one call: 46 exported
@@ -44,7 +45,7 @@ extern "C" {
 #endif
 
 #define FCAMD_VERSION_MAJOR 0
-#define FCAMD_VERSION_MINOR 4
+#define FCAMD_VERSION_MINOR 5
 
 /* ---- status codes (mapped to Python exceptions by the ctypes shim) -------- */
 typedef enum fcamd_status {
@@ -225,7 +226,7 @@ FCAMD_API int fcamd_evaluate_host(fcamd_model* model, double t, double del_t, in
                      over all local iterations, the plastic count is the last iterate's.  Out-of-plane shear
                      stresses are not enforced: they are unmapped components of the cache (zero for the isotropic
                      laws from a zero cache).  Any other wrapper_constraint: FCAMD_ERR_BAD_ARG;
-     flags           FCAMD_EVAL_* below. */
+     flags           FCAMD_EVAL_* below (FCAMD_EVAL_PARAM_FIELDS: per-point material parameters). */
 typedef struct fcamd_eval_args {
     const double* grad_del_u;
     const double* stress_prev;
@@ -248,7 +249,8 @@ typedef struct fcamd_eval_args {
     uint64_t* packed_mask;              /* ... of the trial array (written); one word per 64-point tile each */
     int wrapper_constraint;             /* 0, or FCAMD_UNIAXIAL_STRAIN / FCAMD_PLANE_STRAIN / FCAMD_PLANE_STRESS /
                                            FCAMD_UNIAXIAL_STRESS: the fused 3D wrapper form */
-    double* stress_3d;                  /* the wrapper's cached 3-D stress (6 n), with wrapper_constraint */
+    double* stress_3d;                  /* the wrapper's cached 3-D stress (6 n), with wrapper_constraint --
+                                           with FCAMD_EVAL_PARAM_FIELDS: the parameter-field table (fcamd_eval_args_set_param_fields) */
 } fcamd_eval_args;
 /* Layout of a counter buffer: FCAMD_COUNTER_SLOTS slots of 4 words {non-converged points, plastic
    points, Newton iterations, points outside the law's domain}; the totals (fcamd_stats) are the sums
@@ -285,6 +287,19 @@ typedef struct fcamd_eval_args {
    and mask word), so the commit is still a swap of pointers -- arrays and mask arrays.  Same values, bit for bit, as the
    unpacked sparse protocol; the scalar history keeps its layout.  ResidentState packs / unpacks at set_state / history. */
 #define FCAMD_EVAL_PACKED_HISTORY 8
+/* Per-point material parameters (ABI 0.5).  The table is a HOST array of the model's n_params entries (the order of
+   fcamd_model_create): entry k NULL -- parameter k is the model's scalar -- or a 16-byte-aligned DEVICE array of n doubles,
+   parameter k of point i at [i].  It travels in `stress_3d`, the member of the fused wrapper form that no other form reads (the
+   struct keeps its ABI 0.4 layout): set both with fcamd_eval_args_set_param_fields below.  All entries NULL: the plain call.
+   Laws: FCAMD_LINEAR_ELASTICITY (FULL constraint), FCAMD_COMFE_LINEAR_ELASTICITY, FCAMD_VON_MISES_3D, FCAMD_COMFE_MISES_PLASTICITY, in
+   every form fcamd_evaluate_device_ex takes for them (in place, out of place, history_mask, the other FCAMD_EVAL_* flags, stress2,
+   counters) except parent_rows and the wrapper form, and in fcamd_evaluate_resident (the tangent then always comes from the kernel,
+   never from the host threads of "host_tangent_threads").  The law's constants are derived per point from the raw values with the
+   expressions of the scalar model, so a field whose entries all equal v gives the bits of the model created with v.  The arrays
+   are read, never written; the sparse-tangent protocol stays valid as long as they do not change between the calls that rely on
+   it.  Refused with FCAMD_ERR_UNSUPPORTED, nothing launched: the other laws and constraints, parent_rows, the wrapper form and
+   fcamd_evaluate_batch; a misaligned field: FCAMD_ERR_ALIGN. */
+#define FCAMD_EVAL_PARAM_FIELDS 16
 FCAMD_API int fcamd_evaluate_device_ex(fcamd_model* model, double t, double del_t, int64_t n,
                                        const fcamd_eval_args* args);
 
@@ -604,6 +619,12 @@ FCAMD_INLINE int fcamd_evaluate_device_wrapped(fcamd_model* model, int wrapper_c
     x.history_prev = (const double* const*)history, x.history = history, x.n_hist = n_hist;
     x.wrapper_constraint = wrapper_constraint ? wrapper_constraint : -1, x.stress_3d = stress_3d;
     return fcamd_evaluate_device_ex(model, t, del_t, n, &x);
+}
+
+/* FCAMD_EVAL_PARAM_FIELDS: `fields` (n_params entries, see there) as the call's per-point parameters; NULL: none */
+FCAMD_INLINE void fcamd_eval_args_set_param_fields(fcamd_eval_args* x, const double* const* fields) {
+    x->stress_3d = (double*)(uintptr_t)fields;
+    x->flags = fields ? (x->flags | FCAMD_EVAL_PARAM_FIELDS) : (x->flags & ~FCAMD_EVAL_PARAM_FIELDS);
 }
 
 /* copies, one direction per name */
