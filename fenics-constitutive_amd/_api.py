@@ -20,6 +20,7 @@ from .models import (  # noqa: F401
     SpringMaxwellModel,
     VonMises3D,
 )
+from .userlaw import UserLaw, UserLawCompileError  # noqa: F401
 from .wrappers import PlaneStrainFrom3D, PlaneStressFrom3D, UniaxialStrainFrom3D, UniaxialStressFrom3D  # noqa: F401
 from .utils import get_elastic_tangent, get_identity, lame_parameters, strain_from_grad_u  # noqa: F401
 
@@ -40,6 +41,8 @@ __all__ = [
     "PlaneStrainFrom3D",
     "UniaxialStressFrom3D",
     "PlaneStressFrom3D",
+    "UserLaw",
+    "UserLawCompileError",
     "lame_parameters",
     "get_elastic_tangent",
     "get_identity",

@@ -43,6 +43,9 @@ class MultiDeviceResidentState:
 
     def __init__(self, law: DeviceLaw, n: int, devices=None, stress0=None, history0=None, split_history: bool = True,
                  sparse_tangent: bool = True, reuse_constant_tangent: bool = True):
+        from .userlaw import refuse_user_law
+
+        refuse_user_law(law, "MultiDeviceResidentState")
         if law.field_points is not None:
             raise NotImplementedError("MultiDeviceResidentState: laws with per-point parameter fields are not supported")
         if devices is None:

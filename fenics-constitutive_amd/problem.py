@@ -120,7 +120,10 @@ class ResidentProblemState:
         import torch
 
         from . import _capi
+        from .userlaw import refuse_user_law
 
+        for law in ([laws] if not isinstance(laws, (list, tuple)) else [x[0] if isinstance(x, (list, tuple)) else x for x in laws]):
+            refuse_user_law(law, "ResidentProblemState")
         self.device = torch.device("cuda", _capi.default_device()) if device is None else torch.device(device)
         self.n = int(n_points)
         f = dict(dtype=torch.float64, device=self.device)

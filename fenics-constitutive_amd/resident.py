@@ -49,6 +49,9 @@ class ResidentState:
         "auto" (default): "vmm", falling back to "tune" if the virtual-memory API is not available."""
         import torch
 
+        from .userlaw import refuse_user_law
+
+        refuse_user_law(law, "ResidentState")
         assert placement in ("auto", "vmm", "tune", "torch")
         # ``packed_history`` (VonMises3D and -- with ``split_history`` -- the comfe-rs plasticity laws, under the sparse
         # protocol): the plastic-strain array only accumulates (mises_plasticity_isotropic_hardening.py:161,

@@ -1,0 +1,132 @@
+"""Three built-in laws written as ``UserLaw`` point functions: starting points for laws of one's own, and the yardsticks of the
+user-law kernel template (tests/test_gpu_user_law.py, tools/user_law_bench.py).
+
+* ``LINEAR_ELASTICITY``: LinearElasticityModel (FULL) with the library's ``le_entries`` and the ascending-k FMA product -- bit for
+  bit the built-in kernel's stress and tangent.
+* ``SPRING_MAXWELL``: SpringMaxwellModel (FULL), the reference's NumPy expression order (models/spring_maxwell_model.py:56-88).
+* ``VON_MISES_3D``: VonMises3D, the reference's per-point return mapping and Newton stopping rule
+  (models/mises_plasticity_isotropic_hardening.py:74-175); a point whose Newton iteration exceeds 100 steps returns 1.
+"""
+
+from __future__ import annotations
+
+from .interfaces import StressStrainConstraint
+from .userlaw import UserLaw
+
+__all__ = ["LINEAR_ELASTICITY", "SPRING_MAXWELL", "VON_MISES_3D", "linear_elasticity", "spring_maxwell", "von_mises_3d"]
+
+LINEAR_ELASTICITY = r"""
+// sigma += eps @ D ; tangent = D
+__device__ int fcamd_user_point(const UserParams& p, double t, double del_t, const double (&grad)[9], const double (&eps)[6],
+                                double (&sigma)[6], double (&D)[36], UserHistory& h) {
+    fcamd_elastic_matrix(le_entries(p.E, p.nu), D);
+    double ds[6];
+    row_times_matrix_fma(eps, D, ds);
+    for (int i = 0; i < 6; ++i) sigma[i] = sigma[i] + ds[i];
+    return 0;
+}
+"""
+
+SPRING_MAXWELL = r"""
+// "x @ M" of the NumPy law: row_times_matrix_fma (the ascending-k FMA chain of the built-in kernels)
+__device__ int fcamd_user_point(const UserParams& p, double t, double del_t, const double (&grad)[9], const double (&eps)[6],
+                                double (&sigma)[6], double (&D)[36], UserHistory& h) {
+    double D0[36], D1[36], D01[36];
+    fcamd_elastic_matrix(le_entries(p.E0, p.nu), D0);
+    fcamd_elastic_matrix(le_entries(p.E1, p.nu), D1);
+    for (int i = 0; i < 36; ++i) D01[i] = D0[i] + D1[i];
+    const double mu1 = p.E1 / (2.0 * (1.0 + p.nu));
+    const double factor = 1.0 / del_t + 1.0 / p.tau;
+    const double c = 1.0 / (p.tau * 2.0 * mu1);
+    double x[6], y[6], ds[6], dev_v[6];
+    for (int i = 0; i < 6; ++i) x[i] = c * (h.strain[i] + eps[i]);
+    row_times_matrix_fma(x, D1, y);
+    for (int i = 0; i < 6; ++i) dev_v[i] = 1.0 / factor * (y[i] - 1.0 / p.tau * h.strain_visco[i]);
+    row_times_matrix_fma(eps, D01, ds);
+    for (int i = 0; i < 6; ++i) sigma[i] = sigma[i] + (ds[i] - 2.0 * mu1 * dev_v[i]);
+    const double r = 1.0 - 1.0 / (p.tau * factor);
+    for (int i = 0; i < 36; ++i) D[i] = D0[i] + r * D1[i];
+    for (int i = 0; i < 6; ++i) {
+        h.strain_visco[i] = h.strain_visco[i] + dev_v[i];
+        h.strain[i] = h.strain[i] + eps[i];
+    }
+    return 0;
+}
+"""
+
+VON_MISES_3D = r"""
+__device__ int fcamd_user_point(const UserParams& p, double t, double del_t, const double (&grad)[9], const double (&eps)[6],
+                                double (&sigma)[6], double (&D)[36], UserHistory& h) {
+    const double mu = p.p_mu, s23 = sqrt(2.0 / 3.0), dy = p.p_y00 - p.p_y0;
+    const double tr_eps = (eps[0] + eps[1]) + eps[2];
+    const double tr_sig = (sigma[0] + sigma[1]) + sigma[2];
+    double del_sigtr[6], sigtr[6];
+    for (int i = 0; i < 6; ++i) {
+        const double I = i < 3 ? 1.0 : 0.0;
+        del_sigtr[i] = 2.0 * mu * (eps[i] - tr_eps * I / 3.0);
+        sigtr[i] = (sigma[i] - tr_sig * I / 3.0) + del_sigtr[i];
+    }
+    double sq = sigtr[0] * sigtr[0];
+    for (int i = 1; i < 6; ++i) sq = sq + sigtr[i] * sigtr[i];
+    const double sigtrn = sqrt(sq);
+    const double a_n = h.alpha[0];
+    const double phitr = sigtrn - s23 * (p.p_y0 + dy * (1.0 - exp(-p.p_w * a_n)));
+    double xn[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double g1 = 0.0, xc1 = 0.0, xc2 = 0.0;
+    int status = 0;
+    if (phitr > 0.0) {
+        double g0 = 1.0, xr = 1.0;
+        int it = 0;
+        for (int i = 0; i < 6; ++i) xn[i] = sigtr[i] / sigtrn;
+        while (fabs(xr) > 1e-12 && fabs(g1 - g0) > 1e-8 * fabs(g1)) {
+            g0 = g1;
+            ++it;
+            const double ex = exp(-p.p_w * (a_n + s23 * g0));
+            xr = sigtrn - 2.0 * mu * g0 - s23 * (p.p_y0 + dy * (1.0 - ex));
+            const double xg = -2.0 * mu - 2.0 / 3.0 * dy * p.p_w * ex;
+            g1 = g0 - xr / xg;
+            if (it > 100) {
+                status = 1;
+                break;
+            }
+        }
+        const double xg = -2.0 * mu - 2.0 / 3.0 * dy * p.p_w * exp(-p.p_w * (a_n + s23 * g1));
+        xc1 = -1.0 / xg;
+        xc2 = g1 / sigtrn;
+    }
+    for (int i = 0; i < 6; ++i) {
+        const double I = i < 3 ? 1.0 : 0.0;
+        h.eps_n[i] = h.eps_n[i] + g1 * xn[i];
+        sigma[i] = sigma[i] + ((p.p_ka * tr_eps * I + del_sigtr[i]) - 2.0 * mu * g1 * xn[i]);
+    }
+    h.alpha[0] = h.alpha[0] + s23 * g1;
+    const double B = 2.0 * mu * (1.0 - 2.0 * mu * xc2);
+    const double Cc = 4.0 * mu * mu * (xc2 - xc1);
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) {
+            const double ioi = (i < 3 && j < 3) ? 1.0 : 0.0;
+            const double pp = (i == j ? 1.0 : 0.0) - 1.0 / 3.0 * ioi;
+            D[6 * i + j] = (p.p_ka * ioi + B * pp) + Cc * (xn[i] * xn[j]);
+        }
+    return status;
+}
+"""
+
+FULL = StressStrainConstraint.FULL
+
+
+def linear_elasticity(parameters) -> UserLaw:
+    """``parameters``: {"E", "nu"}"""
+    return UserLaw(LINEAR_ELASTICITY, {"E": parameters["E"], "nu": parameters["nu"]}, None, FULL, name="linear_elasticity")
+
+
+def spring_maxwell(parameters) -> UserLaw:
+    """``parameters``: {"E0", "E1", "tau", "nu"}"""
+    return UserLaw(SPRING_MAXWELL, {k: parameters[k] for k in ("E0", "E1", "tau", "nu")}, {"strain_visco": 6, "strain": 6}, FULL,
+                   name="spring_maxwell")
+
+
+def von_mises_3d(parameters) -> UserLaw:
+    """``parameters``: {"p_ka", "p_mu", "p_y0", "p_y00", "p_w"}"""
+    return UserLaw(VON_MISES_3D, {k: parameters[k] for k in ("p_ka", "p_mu", "p_y0", "p_y00", "p_w")}, {"eps_n": 6, "alpha": 1}, FULL,
+                   name="von_mises_3d")
