@@ -7,6 +7,9 @@ kernels' tile code (``csrc/kernels/tile_io.h``) -- by hiprtc, and keeps the code
 there (``hipModuleLoadData`` of the HIP runtime torch has mapped: the process keeps one runtime) and every call launches it
 (``hipModuleLaunchKernel``) on torch's current stream.  Compiling needs no GPU: the arch is fixed.
 
+With ``tangent="autodiff"`` the source defines a stress and history update templated on the scalar type, compiled inside
+``csrc/jit/user_law_ad.hip``; the tangent comes from forward-mode automatic differentiation (``csrc/jit/user_law_ad.h``).
+
 FULL constraint, scalar parameters, ``evaluate`` / ``evaluate_from``: the resident, batched, indexed and multi-GPU forms of the
 built-in laws are refused with ``NotImplementedError``.
 """
@@ -36,6 +39,12 @@ KERNEL = "fcamd_user_law_kernel"
 MAX_PARAMS = 32  # UserArgs.params (user_law.hip: kMaxParams)
 #: register budgets tried in turn (waves per SIMD: 128 / 168 / 256 VGPRs): the first without scratch is kept
 WAVES_PER_SIMD = (4, 3, 2)
+#: tangent kernels of autodiff laws: (waves per SIMD, directions per pass) tried in turn, the first without scratch is kept.  One
+#: pass (K = 6) at any budget first: it writes the tangent as coalesced 16-byte chunks, while K < 6 writes every pass's columns
+#: as 8-byte entries (SpringMaxwellModel: 2.09x the time of K = 6 at 3 instead of 2 waves); then the most waves
+#: with the fewest passes
+AD_LADDER = tuple((w, 6) for w in WAVES_PER_SIMD) + tuple((w, k) for w in WAVES_PER_SIMD for k in (3, 2, 1))
+TANGENT_MODES = ("explicit", "autodiff")
 MAX_HISTORY_DIM = 36  # doubles per point of one history field (user_law.hip: kUserMaxDim)
 FACTOR_PY = float.fromhex("0x1.6a09e667f3bccp-1")  # the off-diagonal Mandel factor of the Python laws (fcamd_capi.cpp: kFactorPy)
 NONCONVERGED_MESSAGE = _capi.status_string(_capi.ERR_NONCONVERGED)
@@ -185,9 +194,10 @@ def parse_resources(log: str) -> dict:
 class _Compiled:
     """one code object and its modules (one per device)"""
 
-    def __init__(self, code: bytes, log: str):
+    def __init__(self, code: bytes, log: str, key: str = ""):
         self.code = code
         self.log = log
+        self.key = key  # the compile cache key
         self.resources = parse_resources(log)
         self._functions = {}  # device -> (module, function)
         self._lock = threading.Lock()
@@ -207,13 +217,15 @@ class _Compiled:
             return f[1]
 
 
-def _compile(program: str, name: str) -> _Compiled:
-    """hiprtc, cached in process by the sha256 of everything the code object depends on (and on disk in ``FCAMD_JIT_CACHE``)"""
+def _compile(program: str, name: str, extra=()) -> _Compiled:
+    """hiprtc, cached in process by the sha256 of everything the code object depends on (and on disk in ``FCAMD_JIT_CACHE``).
+    ``extra``: further files of ``JIT_DIR`` the program includes (the autodiff template and header)."""
     global _compiles
     template, api, tile_io = (_read(os.path.join(JIT_DIR, "user_law.hip")), _read(os.path.join(JIT_DIR, "user_law_api.h")),
                               _read(os.path.join(KERNEL_DIR, "tile_io.h")))
     h = hashlib.sha256()
-    for part in (template, api, tile_io, program, " ".join(OPTIONS), _rtc_version()):
+    for part in (template, api, tile_io, *[_read(os.path.join(JIT_DIR, f)) for f in extra], program, " ".join(OPTIONS),
+                 _rtc_version()):
         h.update(part.encode() + b"\0")
     key = h.hexdigest()
     with _lock:
@@ -225,7 +237,7 @@ def _compile(program: str, name: str) -> _Compiled:
             try:
                 with open(os.path.join(disk, key + ".co"), "rb") as fh:
                     code = fh.read()
-                hit = _cache[key] = _Compiled(code, _read(os.path.join(disk, key + ".log")))
+                hit = _cache[key] = _Compiled(code, _read(os.path.join(disk, key + ".log")), key)
                 return hit
             except OSError:
                 pass
@@ -264,13 +276,16 @@ def _compile(program: str, name: str) -> _Compiled:
                     os.replace(tmp, os.path.join(disk, key + ext))
             except OSError:
                 pass
-        hit = _cache[key] = _Compiled(code, log)
+        hit = _cache[key] = _Compiled(code, log, key)
         return hit
 
 
 # --------------------------------------------------------------------------------------------------------------------------
 # the law
 # --------------------------------------------------------------------------------------------------------------------------
+_AD_FILES = ("user_law_ad.h", "user_law_ad.hip")
+
+
 def _check_name(name, what: str) -> str:
     if not isinstance(name, str) or not _IDENT.match(name):
         raise ValueError(f"UserLaw: {what} name {name!r} is not a C identifier")
@@ -319,10 +334,17 @@ class UserLaw(IncrSmallStrainModel):
 
     ``parameters``: name -> scalar float, at most 32; the values are kernel arguments, so laws that differ only in them share
     one code object.  ``history_dim``: name -> doubles per point (an int or a tuple, whose product counts), or None.  The
-    names are C identifiers, not C++ keywords, and do not repeat.  FULL constraint only."""
+    names are C identifiers, not C++ keywords, and do not repeat.  FULL constraint only.
+
+    ``tangent``: ``"explicit"`` (the source defines ``fcamd_user_point``, which writes the tangent itself) or ``"autodiff"`` (the
+    source defines the function template ``fcamd_user_stress<T>``, stress and history only; the tangent comes from forward-mode
+    automatic differentiation, contract in ``csrc/jit/user_law_ad.h``)."""
 
     def __init__(self, source: str, parameters=None, history_dim=None, constraint: StressStrainConstraint = None,
-                 name: str = "user_law"):
+                 name: str = "user_law", tangent: str = "explicit"):
+        if not isinstance(tangent, str) or tangent not in TANGENT_MODES:
+            raise ValueError(f"UserLaw: tangent={tangent!r}; expected one of {TANGENT_MODES}")
+        self.tangent_mode = tangent
         constraint = StressStrainConstraint.FULL if constraint is None else constraint
         if constraint != StressStrainConstraint.FULL:
             raise NotImplementedError(f"UserLaw: constraint {constraint.name}: user laws are FULL (3-D) only; wrap one in "
@@ -345,14 +367,29 @@ class UserLaw(IncrSmallStrainModel):
         self._history_dim = history_dim
         self._hist = [(n, _dim_value(n, d)) for n, d in hist]
         self.source = source
-        # cut for 4 waves per SIMD (128 VGPRs; the LDS allows no more); a law that spills there is compiled again for fewer waves
-        for waves in WAVES_PER_SIMD:
-            self._compiled = _compile(self._program(source, waves), self.name)
-            if not self._compiled.resources.get("scratch_bytes"):
-                break
-        if self.resources.get("scratch_bytes"):
-            warnings.warn(f"UserLaw '{self.name}': the kernel uses {self.resources['scratch_bytes']} bytes of scratch per lane "
-                          f"(VGPRs: {self.resources.get('vgprs')}); register spills cost memory bandwidth", UserWarning, stacklevel=2)
+        self._directions = None
+        if tangent == "explicit":
+            # cut for 4 waves per SIMD (128 VGPRs; the LDS allows no more); a law that spills there is compiled again for fewer waves
+            for waves in WAVES_PER_SIMD:
+                self._compiled = _compile(self._program(source, waves), self.name)
+                if not self._compiled.resources.get("scratch_bytes"):
+                    break
+            self._compiled_stress = self._compiled
+        else:
+            # two code objects: the stress-only kernel (T = double) for tangent=None launches, the tangent kernel (Dual<K>)
+            for waves in WAVES_PER_SIMD:
+                self._compiled_stress = _compile(self._program_ad(source, waves, 0), self.name, _AD_FILES)
+                if not self._compiled_stress.resources.get("scratch_bytes"):
+                    break
+            for waves, k in AD_LADDER:
+                self._compiled = _compile(self._program_ad(source, waves, k), self.name, _AD_FILES)
+                self._directions = k
+                if not self._compiled.resources.get("scratch_bytes"):
+                    break
+        for c in {id(self._compiled): self._compiled, id(self._compiled_stress): self._compiled_stress}.values():
+            if c.resources.get("scratch_bytes"):
+                warnings.warn(f"UserLaw '{self.name}': the kernel uses {c.resources['scratch_bytes']} bytes of scratch per lane "
+                              f"(VGPRs: {c.resources.get('vgprs')}); register spills cost memory bandwidth", UserWarning, stacklevel=2)
         self._counters = {}  # device -> int64 device word (non-converged points of the last launch)
         self._empty = {}  # device -> the last call had no points
         self._args_cls = _args_type(max(1, len(self._hist)))
@@ -374,10 +411,34 @@ class UserLaw(IncrSmallStrainModel):
                  '#line 1 "' + re.sub(r'[^A-Za-z0-9_.]', '_', self.name) + '"']
         return "\n".join(lines) + "\n" + source + '\n#include "user_law.hip"\n'
 
+    def _program_ad(self, source: str, waves: int, directions: int) -> str:
+        """autodiff mode: the generated definitions, the user's template, the autodiff kernel template (``directions``: partials
+        per Dual, 0 for the stress-only kernel)"""
+        p = self._param_names
+        lines = ['#include "user_law_ad.h"',
+                 f"#define FCAMD_USER_WAVES {waves}",
+                 f"#define FCAMD_USER_AD_K {directions}",
+                 f"#define FCAMD_USER_NHIST {len(self._hist)}",
+                 "#define FCAMD_USER_HISTORY_FIELDS(X) " + " ".join(f"X({k}, {n}, {d})" for k, (n, d) in enumerate(self._hist)),
+                 "struct UserParams {" + "".join(f" double {n};" for n in p) + " };",
+                 "template <class T> struct UserHistoryT {" + "".join(f" T {n}[{d}];" for n, d in self._hist) + " };",
+                 "__device__ __forceinline__ UserParams fcamd_user_params(const double* v) {",
+                 "    UserParams p;" + "".join(f" p.{n} = v[{k}];" for k, n in enumerate(p)),
+                 "    return p;",
+                 "}",
+                 '#line 1 "' + re.sub(r'[^A-Za-z0-9_.]', '_', self.name) + '"']
+        return "\n".join(lines) + "\n" + source + '\n#include "user_law_ad.hip"\n'
+
     @property
     def resources(self) -> dict:
-        """``{"vgprs", "sgprs", "scratch_bytes", "waves_per_simd", ...}`` of the compiled kernel (compiler remarks)"""
-        return dict(self._compiled.resources)
+        """``{"vgprs", "sgprs", "scratch_bytes", "waves_per_simd", ...}`` of the compiled kernel (compiler remarks).  Autodiff
+        laws: those of the tangent kernel, its ``"directions_per_pass"`` (K of Dual<K>; ceil(6 / K) passes) and under
+        ``"stress_only"`` those of the kernel of tangent=None launches."""
+        r = dict(self._compiled.resources)
+        if self._directions is not None:
+            r["directions_per_pass"] = self._directions
+            r["stress_only"] = dict(self._compiled_stress.resources)
+        return r
 
     @property
     def compile_log(self) -> str:
@@ -519,7 +580,7 @@ class UserLaw(IncrSmallStrainModel):
             return
         counter = self._counter(dev)
         counter.zero_()  # on torch's current stream: the launch's stream
-        fn = self._compiled.function(dev)
+        fn = (self._compiled if tangent is not None else self._compiled_stress).function(dev)
         a = self._args_cls()
         a.grad, a.stress_in, a.stress_out = grad.data_ptr(), stress_prev.data_ptr(), stress.data_ptr()
         a.tangent = None if tangent is None else tangent.data_ptr()

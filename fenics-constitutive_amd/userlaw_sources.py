@@ -6,6 +6,14 @@ user-law kernel template (tests/test_gpu_user_law.py, tools/user_law_bench.py).
 * ``SPRING_MAXWELL``: SpringMaxwellModel (FULL), the reference's NumPy expression order (models/spring_maxwell_model.py:56-88).
 * ``VON_MISES_3D``: VonMises3D, the reference's per-point return mapping and Newton stopping rule
   (models/mises_plasticity_isotropic_hardening.py:74-175); a point whose Newton iteration exceeds 100 steps returns 1.
+
+The same three in autodiff form (``tangent="autodiff"``: stress and history only, the tangent by forward-mode automatic
+differentiation; contract in ``csrc/jit/user_law_ad.h``), each in the expression order of its explicit form, so stress and
+history are bit-identical to it: ``LINEAR_ELASTICITY_AD``, ``SPRING_MAXWELL_AD``, ``VON_MISES_3D_AD``.  And one law the engine
+does not ship, in autodiff form only:
+
+* ``VON_MISES_SWIFT_AD``: von Mises plasticity with Swift hardening, yield stress ``K (eps0 + alpha)^m``, radial return with a
+  per-point Newton iteration on the plastic multiplier; a point that has not converged after ``max_iter`` steps returns 1.
 """
 
 from __future__ import annotations
@@ -13,7 +21,9 @@ from __future__ import annotations
 from .interfaces import StressStrainConstraint
 from .userlaw import UserLaw
 
-__all__ = ["LINEAR_ELASTICITY", "SPRING_MAXWELL", "VON_MISES_3D", "linear_elasticity", "spring_maxwell", "von_mises_3d"]
+__all__ = ["LINEAR_ELASTICITY", "SPRING_MAXWELL", "VON_MISES_3D", "linear_elasticity", "spring_maxwell", "von_mises_3d",
+           "LINEAR_ELASTICITY_AD", "SPRING_MAXWELL_AD", "VON_MISES_3D_AD", "VON_MISES_SWIFT_AD", "linear_elasticity_ad",
+           "spring_maxwell_ad", "von_mises_3d_ad", "von_mises_swift_ad"]
 
 LINEAR_ELASTICITY = r"""
 // sigma += eps @ D ; tangent = D
@@ -112,6 +122,140 @@ __device__ int fcamd_user_point(const UserParams& p, double t, double del_t, con
 }
 """
 
+LINEAR_ELASTICITY_AD = r"""
+// sigma += eps @ D: the ascending-k FMA chain; its derivative with a unit seed in eps_j is exactly row j of D
+template <class T>
+__device__ int fcamd_user_stress(const UserParams& p, double t, double del_t, const T (&eps)[6], T (&sigma)[6], UserHistoryT<T>& h) {
+    double D[36];
+    fcamd_elastic_matrix(le_entries(p.E, p.nu), D);
+    T ds[6];
+    row_times_matrix_fma(eps, D, ds);
+    for (int i = 0; i < 6; ++i) sigma[i] = sigma[i] + ds[i];
+    return 0;
+}
+"""
+
+SPRING_MAXWELL_AD = r"""
+template <class T>
+__device__ int fcamd_user_stress(const UserParams& p, double t, double del_t, const T (&eps)[6], T (&sigma)[6], UserHistoryT<T>& h) {
+    double D0[36], D1[36], D01[36];
+    fcamd_elastic_matrix(le_entries(p.E0, p.nu), D0);
+    fcamd_elastic_matrix(le_entries(p.E1, p.nu), D1);
+    for (int i = 0; i < 36; ++i) D01[i] = D0[i] + D1[i];
+    const double mu1 = p.E1 / (2.0 * (1.0 + p.nu));
+    const double factor = 1.0 / del_t + 1.0 / p.tau;
+    const double c = 1.0 / (p.tau * 2.0 * mu1);
+    T x[6], y[6], ds[6], dev_v[6];
+    for (int i = 0; i < 6; ++i) x[i] = c * (h.strain[i] + eps[i]);
+    row_times_matrix_fma(x, D1, y);
+    for (int i = 0; i < 6; ++i) dev_v[i] = 1.0 / factor * (y[i] - 1.0 / p.tau * h.strain_visco[i]);
+    row_times_matrix_fma(eps, D01, ds);
+    for (int i = 0; i < 6; ++i) sigma[i] = sigma[i] + (ds[i] - 2.0 * mu1 * dev_v[i]);
+    for (int i = 0; i < 6; ++i) {
+        h.strain_visco[i] = h.strain_visco[i] + dev_v[i];
+        h.strain[i] = h.strain[i] + eps[i];
+    }
+    return 0;
+}
+"""
+
+VON_MISES_3D_AD = r"""
+// the return mapping of VON_MISES_3D without its tangent block: the Newton loop is differentiated through its iterations
+template <class T>
+__device__ int fcamd_user_stress(const UserParams& p, double t, double del_t, const T (&eps)[6], T (&sigma)[6], UserHistoryT<T>& h) {
+    const double mu = p.p_mu, s23 = sqrt(2.0 / 3.0), dy = p.p_y00 - p.p_y0;
+    const T tr_eps = (eps[0] + eps[1]) + eps[2];
+    const T tr_sig = (sigma[0] + sigma[1]) + sigma[2];
+    T del_sigtr[6], sigtr[6];
+    for (int i = 0; i < 6; ++i) {
+        const double I = i < 3 ? 1.0 : 0.0;
+        del_sigtr[i] = 2.0 * mu * (eps[i] - tr_eps * I / 3.0);
+        sigtr[i] = (sigma[i] - tr_sig * I / 3.0) + del_sigtr[i];
+    }
+    T sq = sigtr[0] * sigtr[0];
+    for (int i = 1; i < 6; ++i) sq = sq + sigtr[i] * sigtr[i];
+    const T sigtrn = sqrt(sq);
+    const T a_n = h.alpha[0];
+    const T phitr = sigtrn - s23 * (p.p_y0 + dy * (1.0 - exp(-p.p_w * a_n)));
+    T xn[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    T g1 = 0.0;
+    int status = 0;
+    if (phitr > 0.0) {
+        T g0 = 1.0, xr = 1.0;
+        int it = 0;
+        for (int i = 0; i < 6; ++i) xn[i] = sigtr[i] / sigtrn;
+        while (fabs(xr) > 1e-12 && fabs(g1 - g0) > 1e-8 * fabs(g1)) {
+            g0 = g1;
+            ++it;
+            const T ex = exp(-p.p_w * (a_n + s23 * g0));
+            xr = sigtrn - 2.0 * mu * g0 - s23 * (p.p_y0 + dy * (1.0 - ex));
+            const T xg = -2.0 * mu - 2.0 / 3.0 * dy * p.p_w * ex;
+            g1 = g0 - xr / xg;
+            if (it > 100) {
+                status = 1;
+                break;
+            }
+        }
+    }
+    for (int i = 0; i < 6; ++i) {
+        const double I = i < 3 ? 1.0 : 0.0;
+        h.eps_n[i] = h.eps_n[i] + g1 * xn[i];
+        sigma[i] = sigma[i] + ((p.p_ka * tr_eps * I + del_sigtr[i]) - 2.0 * mu * g1 * xn[i]);
+    }
+    h.alpha[0] = h.alpha[0] + s23 * g1;
+    return status;
+}
+"""
+
+VON_MISES_SWIFT_AD = r"""
+// von Mises plasticity with Swift hardening, sigma_y = K (eps0 + alpha)^m: radial return, Newton on the plastic multiplier g
+// of r(g) = |s_tr| - 2 mu g - sqrt(2/3) sigma_y(alpha_n + sqrt(2/3) g).  Converged when |r| <= 1e-10 sigma_y, after which one
+// more Newton step is taken (its derivative is then the implicit one to rounding); more than max_iter steps: status 1.
+template <class T>
+__device__ int fcamd_user_stress(const UserParams& p, double t, double del_t, const T (&eps)[6], T (&sigma)[6], UserHistoryT<T>& h) {
+    const double mu = p.p_mu, s23 = sqrt(2.0 / 3.0);
+    const T tr_eps = (eps[0] + eps[1]) + eps[2];
+    const T tr_sig = (sigma[0] + sigma[1]) + sigma[2];
+    T del_sigtr[6], sigtr[6];
+    for (int i = 0; i < 6; ++i) {
+        const double I = i < 3 ? 1.0 : 0.0;
+        del_sigtr[i] = 2.0 * mu * (eps[i] - tr_eps * I / 3.0);
+        sigtr[i] = (sigma[i] - tr_sig * I / 3.0) + del_sigtr[i];
+    }
+    T sq = sigtr[0] * sigtr[0];
+    for (int i = 1; i < 6; ++i) sq = sq + sigtr[i] * sigtr[i];
+    const T sigtrn = sqrt(sq);
+    const T a0 = p.eps0 + h.alpha[0];
+    const T phitr = sigtrn - s23 * (p.K * pow(a0, p.m));
+    T xn[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    T g = 0.0;
+    int status = 0;
+    if (phitr > 0.0) {
+        for (int i = 0; i < 6; ++i) xn[i] = sigtr[i] / sigtrn;
+        for (int it = 0;; ++it) {
+            const T a = a0 + s23 * g;
+            const T sy = p.K * pow(a, p.m);
+            const T r = (sigtrn - 2.0 * mu * g) - s23 * sy;
+            const bool done = fabs(r) <= 1e-10 * sy;
+            if (!done && it >= p.max_iter) {
+                status = 1;
+                break;
+            }
+            const T dr = -2.0 * mu - 2.0 / 3.0 * p.m * (sy / a);
+            g = g - r / dr;
+            if (done) break;
+        }
+    }
+    for (int i = 0; i < 6; ++i) {
+        const double I = i < 3 ? 1.0 : 0.0;
+        h.eps_n[i] = h.eps_n[i] + g * xn[i];
+        sigma[i] = sigma[i] + ((p.p_ka * tr_eps * I + del_sigtr[i]) - 2.0 * mu * g * xn[i]);
+    }
+    h.alpha[0] = h.alpha[0] + s23 * g;
+    return status;
+}
+"""
+
 FULL = StressStrainConstraint.FULL
 
 
@@ -130,3 +274,28 @@ def von_mises_3d(parameters) -> UserLaw:
     """``parameters``: {"p_ka", "p_mu", "p_y0", "p_y00", "p_w"}"""
     return UserLaw(VON_MISES_3D, {k: parameters[k] for k in ("p_ka", "p_mu", "p_y0", "p_y00", "p_w")}, {"eps_n": 6, "alpha": 1}, FULL,
                    name="von_mises_3d")
+
+
+def linear_elasticity_ad(parameters) -> UserLaw:
+    """``parameters``: {"E", "nu"}"""
+    return UserLaw(LINEAR_ELASTICITY_AD, {"E": parameters["E"], "nu": parameters["nu"]}, None, FULL, name="linear_elasticity_ad",
+                   tangent="autodiff")
+
+
+def spring_maxwell_ad(parameters) -> UserLaw:
+    """``parameters``: {"E0", "E1", "tau", "nu"}"""
+    return UserLaw(SPRING_MAXWELL_AD, {k: parameters[k] for k in ("E0", "E1", "tau", "nu")}, {"strain_visco": 6, "strain": 6}, FULL,
+                   name="spring_maxwell_ad", tangent="autodiff")
+
+
+def von_mises_3d_ad(parameters) -> UserLaw:
+    """``parameters``: {"p_ka", "p_mu", "p_y0", "p_y00", "p_w"}"""
+    return UserLaw(VON_MISES_3D_AD, {k: parameters[k] for k in ("p_ka", "p_mu", "p_y0", "p_y00", "p_w")}, {"eps_n": 6, "alpha": 1},
+                   FULL, name="von_mises_3d_ad", tangent="autodiff")
+
+
+def von_mises_swift_ad(parameters) -> UserLaw:
+    """``parameters``: {"p_ka", "p_mu", "K", "eps0", "m"} and optionally "max_iter" (Newton steps; default 50)"""
+    p = {k: parameters[k] for k in ("p_ka", "p_mu", "K", "eps0", "m")}
+    p["max_iter"] = float(parameters.get("max_iter", 50))
+    return UserLaw(VON_MISES_SWIFT_AD, p, {"eps_n": 6, "alpha": 1}, FULL, name="von_mises_swift_ad", tangent="autodiff")
