@@ -21,6 +21,7 @@ from .models import (  # noqa: F401
     VonMises3D,
 )
 from .userlaw import UserLaw, UserLawCompileError  # noqa: F401
+from .objective import JaumannRate  # noqa: F401
 from .wrappers import PlaneStrainFrom3D, PlaneStressFrom3D, UniaxialStrainFrom3D, UniaxialStressFrom3D  # noqa: F401
 from .utils import get_elastic_tangent, get_identity, lame_parameters, strain_from_grad_u  # noqa: F401
 
@@ -43,6 +44,7 @@ __all__ = [
     "PlaneStressFrom3D",
     "UserLaw",
     "UserLawCompileError",
+    "JaumannRate",
     "lame_parameters",
     "get_elastic_tangent",
     "get_identity",

@@ -164,6 +164,9 @@ __device__ __forceinline__ unsigned long long user_tile(const UserArgs& a, const
 #define FCAMD_X(k, name, dim) user_in<dim>(c_##name, region, lane, h.name);
     FCAMD_USER_HISTORY_FIELDS(FCAMD_X)
 #undef FCAMD_X
+#ifdef FCAMD_USER_ROTATE
+    fcamd_user_rotate(g, s, h);  // objective rate (rotation.h): the double committed state, before any Dual is seeded
+#endif
     mandel_strain(g, a.factor, e);
     const bool live = FULL || lane < npts;
     if constexpr (kK == 0) {

@@ -1,0 +1,346 @@
+"""Objective stress rates: ``JaumannRate`` wraps a FULL small-strain law so that its committed stress and tensor-valued history
+turn with the material between increments (the Jaumann rate, integrated with the Hughes-Winget rotation).
+
+Every call takes the incremental spin ``W = (G - G^T) / 2`` of ``G = grad_del_u``, forms ``R = (I - W / 2)^-1 (I + W / 2)``,
+rotates the committed stress and every rotatable history block to ``R S R^T`` and evaluates the law on the rotated state with
+the unchanged strain increment -- what an Abaqus host does to STRESS and the tensor state variables before it calls a UMAT.
+The math and its device code: ``csrc/jit/rotation.h``.
+
+Two paths:
+
+* fused: the rotation runs in registers inside the law's own kernel, between the transposition of the state and the point
+  function (no extra bytes per point).  For ``UserLaw`` (both tangent modes) and, through their ``userlaw_sources``
+  transcriptions, ``LinearElasticityModel`` (FULL), ``SpringMaxwellModel`` (FULL) and ``VonMises3D`` with scalar parameters.
+* array-level: every other FULL law of the package (``SpringKelvinModel``, the comfe-rs laws, laws with parameter fields).
+  A standalone kernel (``csrc/jit/rotate_state.hip``) writes the rotated committed state into the arrays the law then
+  evaluates in place.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+
+from . import _capi, userlaw
+from .device import _check_numpy, _check_torch, _current_stream_ptr, _is_torch, _size
+from .interfaces import IncrSmallStrainModel, StressStrainConstraint
+from .userlaw import UserLaw
+
+__all__ = ["JaumannRate", "default_rotatable"]
+
+ROTATE_KERNEL = "fcamd_rotate_state_kernel"
+_ROTATE_FILES = ("rotation.h", "rotate_state.hip")
+
+
+def default_rotatable(model) -> dict:
+    """history name -> offsets of the Mandel 6-vectors that rotate, for the laws the package ships (``{}`` for a UserLaw)"""
+    from . import models as M
+
+    if isinstance(model, M.VonMises3D):
+        return {"eps_n": [0]}  # alpha is a scalar
+    if isinstance(model, (M.SpringMaxwellModel, M.SpringKelvinModel)):
+        return {"strain_visco": [0], "strain": [0]}
+    if isinstance(model, (M.MisesPlasticityLinearHardening3D, M.DruckerPrager3D, M.DruckerPragerHyperbolic3D)):
+        return {"history": [1]}  # [alpha, eps_p(6)]
+    return {}
+
+
+def _history_dims(model) -> list:
+    """[(name, doubles per point)] of the law's history, in its order"""
+    if isinstance(model, UserLaw):
+        return list(model._hist)
+    hd = model.history_dim
+    return [] if hd is None else [(k, int(v)) for k, v in hd.items()]
+
+
+def _blocks(model, rotatable) -> tuple:
+    """((history name, offset), ...) of ``rotatable``, checked against the law's history"""
+    dims = dict(_history_dims(model))
+    out = []
+    for name, offsets in rotatable.items():
+        if name not in dims:
+            raise ValueError(f"JaumannRate: rotatable names history '{name}', which {type(model).__name__} does not have "
+                             f"(history: {sorted(dims)})")
+        if isinstance(offsets, (int, float, str)):
+            raise ValueError(f"JaumannRate: rotatable['{name}'] must be a list of offsets, not {offsets!r}")
+        taken = set()
+        for off in offsets:
+            if isinstance(off, bool) or not hasattr(off, "__index__"):
+                raise ValueError(f"JaumannRate: rotatable['{name}'] offset {off!r} is not an integer")
+            off = off.__index__()
+            if off < 0 or off + 6 > dims[name]:
+                raise ValueError(f"JaumannRate: the Mandel block at offset {off} of history '{name}' runs past the end of its "
+                                 f"{dims[name]} doubles per point")
+            if taken & set(range(off, off + 6)):
+                raise ValueError(f"JaumannRate: the blocks of history '{name}' overlap at offset {off}")
+            taken |= set(range(off, off + 6))
+            out.append((name, off))
+    return tuple(out)
+
+
+def _fused_law(model, blocks):
+    """the law with the rotation compiled into its kernel, or None where only the array-level path exists"""
+    from . import models as M
+    from . import userlaw_sources as S
+
+    if isinstance(model, UserLaw):
+        return UserLaw(model.source, list(zip(model._param_names, model._param_values)), model._history_dim, model.constraint,
+                       name=model.name, tangent=model.tangent_mode, _rotate=blocks)
+    if getattr(model, "field_points", None) is not None:
+        return None
+    if type(model) is M.LinearElasticityModel:
+        src, p, hist = S.LINEAR_ELASTICITY, dict(zip(("E", "nu"), model._parameter_vector)), None
+    elif type(model) is M.SpringMaxwellModel:
+        src, p = S.SPRING_MAXWELL, {"E0": model.E0, "E1": model.E1, "tau": model.tau, "nu": model.nu}
+        hist = {"strain_visco": 6, "strain": 6}
+    elif type(model) is M.VonMises3D:
+        src = S.VON_MISES_3D
+        p = {k: getattr(model, k) for k in ("p_ka", "p_mu", "p_y0", "p_y00", "p_w")}
+        hist = {"eps_n": 6, "alpha": 1}
+    else:
+        return None
+    name = {S.LINEAR_ELASTICITY: "linear_elasticity", S.SPRING_MAXWELL: "spring_maxwell", S.VON_MISES_3D: "von_mises_3d"}[src]
+    return UserLaw(src, p, hist, StressStrainConstraint.FULL, name=name, _rotate=blocks)
+
+
+class JaumannRate(IncrSmallStrainModel):
+    """A FULL ``IncrSmallStrainModel`` of this package whose committed state is rotated with the material before every
+    evaluation (Jaumann rate, Hughes-Winget rotation; module docstring).
+
+    ``rotatable``: history name -> list of offsets, each the start of a Mandel 6-vector ``[xx, yy, zz, r xy, r xz, r yz]``
+    (r = sqrt(2)) inside that field's per-point row; None takes ``default_rotatable(model)``.  The stress always rotates.
+
+    ``G = grad_del_u`` means what the caller means by it: in an updated-Lagrangian loop, the gradient of the displacement
+    increment on the current configuration.  The tangent is the law's ``d sigma / d delta eps`` at the rotated state (the UMAT
+    convention): it has no geometric or spin term.
+
+    ``evaluate`` (NumPy arrays or device tensors, in place) and ``evaluate_from`` (device tensors, out of place: the committed
+    arrays are left untouched) as the wrapped law.  Refused with ``NotImplementedError``: ``ResidentState``,
+    ``ResidentProblemState``, ``MultiDeviceResidentState``, ``batched_launches``, ``evaluate_indexed`` and the ``*From3D``
+    wrappers.  ``fused = False`` (on the instance) forces the array-level path."""
+
+    #: use the kernel with the rotation compiled in where one exists; False: the standalone rotation kernel, then the law
+    fused = True
+
+    def __init__(self, model, rotatable=None):
+        from .device import DeviceLaw
+
+        if isinstance(model, JaumannRate):
+            raise ValueError("JaumannRate: the model is a JaumannRate already")
+        if not isinstance(model, (DeviceLaw, UserLaw)):
+            raise NotImplementedError(f"JaumannRate: {type(model).__name__} is not a law of this package (a DeviceLaw or a UserLaw)")
+        if model.constraint != StressStrainConstraint.FULL:
+            raise NotImplementedError(f"JaumannRate: constraint {model.constraint.name}: objective rates need the FULL (3-D) law")
+        if getattr(model, "_devices", None) is not None:
+            self._refuse("a law on several GPUs (use_devices)")
+        self.model = model
+        if rotatable is None:
+            rotatable = default_rotatable(model)
+        if not hasattr(rotatable, "items"):
+            raise ValueError(f"JaumannRate: rotatable must map history names to lists of offsets, not {rotatable!r}")
+        self._blocks = _blocks(model, rotatable)
+        self.rotatable = {}
+        for name, off in self._blocks:
+            self.rotatable.setdefault(name, []).append(off)
+        self._fused = _fused_law(model, self._blocks)
+        self._rot_fields = [(name, dim) for name, dim in _history_dims(model) if any(b[0] == name for b in self._blocks)]
+        self._rot = None  # the standalone rotation kernel, compiled on first use
+        self._last = model  # the law that ran last (device_stats)
+
+    @staticmethod
+    def _refuse(what: str):
+        raise NotImplementedError(f"JaumannRate: {what} is not supported for objective-rate wrappers")
+
+    # -- interface ------------------------------------------------------------------------------------------------------
+    @property
+    def constraint(self) -> StressStrainConstraint:
+        return StressStrainConstraint.FULL
+
+    @property
+    def history_dim(self):
+        return self.model.history_dim
+
+    @property
+    def field_points(self):
+        return getattr(self.model, "field_points", None)
+
+    @property
+    def path(self) -> str:
+        """``"fused"`` or ``"array"``: the path the next call takes"""
+        return "fused" if self.fused and self._fused is not None else "array"
+
+    @property
+    def resources(self) -> dict:
+        """the compiler's resource report of the fused kernel (``UserLaw.resources``), else of the rotation kernel"""
+        if self.path == "fused":
+            return self._fused.resources
+        return dict(self._rotate_kernel().resources)
+
+    def update(self) -> None:
+        self.model.update()
+
+    def use_devices(self, devices):
+        self._refuse("use_devices (several GPUs in one process)")
+
+    def evaluate_indexed(self, *args, **kwargs):
+        self._refuse("evaluate_indexed (parent rows)")
+
+    @staticmethod
+    def _refuse_batched():
+        if getattr(_capi._tls, "batch", None) is not None:
+            JaumannRate._refuse("a call inside batched_launches()")
+
+    def device_stats(self, device: int = 0):
+        """``device_stats`` of the law that ran last on the call's behalf (the fused UserLaw returns its count, a built-in law
+        raises on non-convergence)"""
+        return self._last.device_stats(device)
+
+    # -- evaluate ---------------------------------------------------------------------------------------------------------
+    def _hist(self, history) -> list:
+        dims = _history_dims(self.model)
+        if not dims:
+            return []
+        if history is None:
+            raise ValueError("history must not be None")
+        return [history[name] for name, _ in dims]
+
+    def _spring_checks(self, del_t) -> None:
+        from .models import _SpringBase
+
+        if isinstance(self.model, _SpringBase):
+            assert del_t > 0, "Time step must be defined and positive."
+
+    def evaluate(self, t, del_t, grad_del_u, stress, tangent, history, check: bool = False) -> None:
+        """``IncrSmallStrainModel.evaluate`` with the committed ``stress`` and history rotated first; all in place."""
+        self._refuse_batched()
+        self._spring_checks(del_t)
+        if self.path == "fused":
+            self._last = self._fused
+            self._fused.evaluate(t, del_t, grad_del_u, stress, tangent, history, check=check)
+            return
+        self._last = self.model
+        hist = self._hist(history)
+        n = self._check_sizes(grad_del_u, stress, tangent, hist)
+        if _is_torch(grad_del_u):
+            self._rotate(n, grad_del_u, stress, stress, hist, hist)
+            self.model.evaluate(t, del_t, grad_del_u, stress, tangent, history, check=check)
+            return
+        self._evaluate_host(t, del_t, n, grad_del_u, stress, tangent, history, hist)
+
+    def evaluate_from(self, t, del_t, grad_del_u, stress_prev, stress, tangent, history_prev, history) -> None:
+        """Out-of-place device evaluate: reads the committed state (``stress_prev``, ``history_prev``, never written), rotates
+        it into ``stress`` / ``history`` and evaluates there.  Device tensors only."""
+        self._refuse_batched()
+        self._spring_checks(del_t)
+        if not _is_torch(grad_del_u):
+            raise TypeError("JaumannRate.evaluate_from takes device tensors (use evaluate for NumPy arrays)")
+        if self.path == "fused":
+            self._last = self._fused
+            self._fused.evaluate_from(t, del_t, grad_del_u, stress_prev, stress, tangent, history_prev, history)
+            return
+        self._last = self.model
+        hist, hprev = self._hist(history), self._hist(history_prev)
+        n = self._check_sizes(grad_del_u, stress, tangent, hist)
+        assert _size(stress_prev) == 6 * n, "Stress, strain, and tangent lengths do not match"
+        for (name, dim), h in zip(_history_dims(self.model), hprev):
+            assert _size(h) == n * dim, f"history '{name}' has the wrong length"
+        rotated = {name for name, _ in self._rot_fields}
+        for (name, _), hp, h in zip(_history_dims(self.model), hprev, hist):
+            if name not in rotated:  # the rotation kernel writes the rotated fields; the rest is the committed state as it is
+                _check_torch(f"history['{name}']", h).copy_(_check_torch(f"history_prev['{name}']", hp))
+        self._rotate(n, grad_del_u, stress_prev, stress, hprev, hist)
+        self.model.evaluate(t, del_t, grad_del_u, stress, tangent, history)
+
+    def _check_sizes(self, grad, stress, tangent, hist) -> int:
+        n = _size(grad) // 9
+        assert n == _size(stress) // 6 and (tangent is None or n == _size(tangent) // 36), "Stress, strain, and tangent lengths do not match"
+        assert _size(grad) == n * 9 and _size(stress) == n * 6, "Input arrays are not of the correct length"
+        for (name, dim), h in zip(_history_dims(self.model), hist):
+            assert _size(h) == n * dim, f"history '{name}' has the wrong length"
+        return n
+
+    def _evaluate_host(self, t, del_t, n, grad, stress, tangent, history, hist) -> None:
+        """NumPy arrays: staged through device copies (as the *From3D wrappers do), rotated and evaluated there, back in
+        place; non-convergence raises after the results are written"""
+        import numpy as np
+        import torch
+
+        from .hostio import assign, to_device
+
+        _check_numpy("grad_del_u", grad)
+        _check_numpy("stress", stress)
+        if tangent is not None:
+            _check_numpy("tangent", tangent)
+        for (name, _), h in zip(_history_dims(self.model), hist):
+            _check_numpy(f"history['{name}']", h)
+        if n == 0:
+            return
+        dev = _capi.default_device()
+        d = torch.device("cuda", dev)
+        with torch.cuda.device(d):
+            g = to_device(grad.reshape(-1), d, np.float64)
+            s = to_device(stress.reshape(-1), d, np.float64)
+            tan = None if tangent is None else torch.empty(36 * n, dtype=torch.float64, device=d)
+            hd = [to_device(h.reshape(-1), d, np.float64) for h in hist]
+            h_dev = None if history is None else dict(zip([name for name, _ in _history_dims(self.model)], hd))
+            self._rotate(n, g, s, s, hd, hd)
+            self.model.evaluate(t, del_t, g, s, tan, h_dev)
+            assign(stress.reshape(-1), s)
+            if tangent is not None:
+                assign(tangent.reshape(-1), tan)
+            for h, x in zip(hist, hd):
+                assign(h.reshape(-1), x)
+            count = self.model.device_stats(dev)  # a built-in law raises here
+            if isinstance(self.model, UserLaw):
+                UserLaw._raise(count)
+
+    # -- the standalone rotation kernel ---------------------------------------------------------------------------------
+    def _rotate_kernel(self):
+        if self._rot is None:
+            names = {name: f"f{k}" for k, (name, _) in enumerate(self._rot_fields)}
+            lines = [f"#define FCAMD_ROT_NFIELDS {len(self._rot_fields)}",
+                     "#define FCAMD_ROT_FIELDS(X) " + " ".join(f"X({k}, {names[n]}, {d})" for k, (n, d) in enumerate(self._rot_fields)),
+                     "#define FCAMD_USER_ROTATE(X) " + " ".join(f"X({names[n]}, {o})" for n, o in self._blocks),
+                     "struct RotHistory {" + "".join(f" double {names[n]}[{d}];" for n, d in self._rot_fields) + " };",
+                     '#include "rotate_state.hip"']
+            self._rot = userlaw._compile("\n".join(lines) + "\n", "jaumann_rotate_state", _ROTATE_FILES, ROTATE_KERNEL)
+            if self._rot.resources.get("scratch_bytes"):
+                raise RuntimeError(f"JaumannRate: the rotation kernel uses {self._rot.resources['scratch_bytes']} bytes of scratch")
+        return self._rot
+
+    def _rotate(self, n, grad, stress_in, stress_out, hist_in, hist_out) -> None:
+        """the rotated committed state -> ``stress_out`` and the rotated history fields of ``hist_out`` (asynchronous, on torch's
+        current stream)"""
+        import torch
+
+        rotated = {name for name, _ in self._rot_fields}
+        pairs = [(hi, ho) for (name, _), hi, ho in zip(_history_dims(self.model), hist_in, hist_out) if name in rotated]
+        dev = grad.device.index or 0
+        for label, a in [("grad_del_u", grad), ("stress_prev", stress_in), ("stress", stress_out)] + \
+                [("history", x) for p in pairs for x in p]:
+            _check_torch(label, a)
+            if (a.device.index or 0) != dev:
+                raise ValueError(f"{label} is on {a.device}, grad_del_u on cuda:{dev}")
+        if n == 0:
+            return
+        fn = self._rotate_kernel().function(dev)
+        a = _rotate_args_type(max(1, len(pairs)))()
+        a.grad, a.s_in, a.s_out = grad.data_ptr(), stress_in.data_ptr(), stress_out.data_ptr()
+        for k, (hi, ho) in enumerate(pairs):
+            a.h_in[k], a.h_out[k] = hi.data_ptr(), ho.data_ptr()
+        a.n = n
+        blocks = min((n + 255) // 256, 64 * userlaw._num_cu(dev))
+        params = (C.c_void_p * 1)(C.cast(C.pointer(a), C.c_void_p))
+        hip = userlaw._load_hip()
+        with torch.cuda.device(dev):
+            userlaw._hip_check(hip.hipModuleLaunchKernel(fn, blocks, 1, 1, 256, 1, 1, 0, C.c_void_p(_current_stream_ptr(dev)),
+                                                         params, None), "JaumannRate rotation launch")
+
+
+def _rotate_args_type(nf: int):
+    """ctypes mirror of RotateArgs (rotate_state.hip) for ``nf`` history slots"""
+    vp = C.c_void_p
+
+    class RotateArgs(C.Structure):
+        _fields_ = [("grad", vp), ("s_in", vp), ("s_out", vp), ("h_in", vp * nf), ("h_out", vp * nf), ("n", C.c_int64)]
+
+    return RotateArgs

@@ -194,10 +194,11 @@ def parse_resources(log: str) -> dict:
 class _Compiled:
     """one code object and its modules (one per device)"""
 
-    def __init__(self, code: bytes, log: str, key: str = ""):
+    def __init__(self, code: bytes, log: str, key: str = "", kernel: str = KERNEL):
         self.code = code
         self.log = log
         self.key = key  # the compile cache key
+        self.kernel = kernel
         self.resources = parse_resources(log)
         self._functions = {}  # device -> (module, function)
         self._lock = threading.Lock()
@@ -212,19 +213,31 @@ class _Compiled:
                 module, fn = C.c_void_p(), C.c_void_p()
                 with torch.cuda.device(device):
                     _hip_check(hip.hipModuleLoadData(C.byref(module), C.c_char_p(self.code)), "hipModuleLoadData")
-                    _hip_check(hip.hipModuleGetFunction(C.byref(fn), module, KERNEL.encode()), "hipModuleGetFunction")
+                    _hip_check(hip.hipModuleGetFunction(C.byref(fn), module, self.kernel.encode()), "hipModuleGetFunction")
                 f = self._functions[device] = (module, fn)
             return f[1]
 
 
-def _compile(program: str, name: str, extra=()) -> _Compiled:
+# the objective-rate hook of the autodiff template (rotation.h); a program that does not define FCAMD_USER_ROTATE never sees it
+_ROTATE_HOOK = re.compile(r"#ifdef FCAMD_USER_ROTATE\n.*?#endif\n", re.S)
+
+
+def _key_text(path: str, program: str) -> str:
+    """the text of an included file as the cache key counts it: without the rotation hook when the program has no rotation,
+    so that the keys of unrotated laws stay what they were before the hook existed"""
+    text = _read(path)
+    return text if "FCAMD_USER_ROTATE" in program else _ROTATE_HOOK.sub("", text)
+
+
+def _compile(program: str, name: str, extra=(), kernel: str = KERNEL) -> _Compiled:
     """hiprtc, cached in process by the sha256 of everything the code object depends on (and on disk in ``FCAMD_JIT_CACHE``).
-    ``extra``: further files of ``JIT_DIR`` the program includes (the autodiff template and header)."""
+    ``extra``: further files of ``JIT_DIR`` the program includes (the autodiff template and header, rotation.h).  ``kernel``:
+    the name of the program's kernel."""
     global _compiles
     template, api, tile_io = (_read(os.path.join(JIT_DIR, "user_law.hip")), _read(os.path.join(JIT_DIR, "user_law_api.h")),
                               _read(os.path.join(KERNEL_DIR, "tile_io.h")))
     h = hashlib.sha256()
-    for part in (template, api, tile_io, *[_read(os.path.join(JIT_DIR, f)) for f in extra], program, " ".join(OPTIONS),
+    for part in (template, api, tile_io, *[_key_text(os.path.join(JIT_DIR, f), program) for f in extra], program, " ".join(OPTIONS),
                  _rtc_version()):
         h.update(part.encode() + b"\0")
     key = h.hexdigest()
@@ -237,7 +250,7 @@ def _compile(program: str, name: str, extra=()) -> _Compiled:
             try:
                 with open(os.path.join(disk, key + ".co"), "rb") as fh:
                     code = fh.read()
-                hit = _cache[key] = _Compiled(code, _read(os.path.join(disk, key + ".log")), key)
+                hit = _cache[key] = _Compiled(code, _read(os.path.join(disk, key + ".log")), key, kernel)
                 return hit
             except OSError:
                 pass
@@ -276,7 +289,7 @@ def _compile(program: str, name: str, extra=()) -> _Compiled:
                     os.replace(tmp, os.path.join(disk, key + ext))
             except OSError:
                 pass
-        hit = _cache[key] = _Compiled(code, log, key)
+        hit = _cache[key] = _Compiled(code, log, key, kernel)
         return hit
 
 
@@ -284,6 +297,7 @@ def _compile(program: str, name: str, extra=()) -> _Compiled:
 # the law
 # --------------------------------------------------------------------------------------------------------------------------
 _AD_FILES = ("user_law_ad.h", "user_law_ad.hip")
+_ROTATION_FILES = ("rotation.h",)
 
 
 def _check_name(name, what: str) -> str:
@@ -323,9 +337,13 @@ def _refuse(what: str):
 
 
 def refuse_user_law(law, what: str) -> None:
-    """the forms of the built-in laws that user laws do not have (resident and multi-GPU states)"""
+    """the forms of the built-in laws that user laws and objective-rate wrappers do not have (resident and multi-GPU states)"""
     if isinstance(law, UserLaw):
         _refuse(what)
+    from .objective import JaumannRate
+
+    if isinstance(law, JaumannRate):
+        JaumannRate._refuse(what)
 
 
 class UserLaw(IncrSmallStrainModel):
@@ -341,7 +359,7 @@ class UserLaw(IncrSmallStrainModel):
     automatic differentiation, contract in ``csrc/jit/user_law_ad.h``)."""
 
     def __init__(self, source: str, parameters=None, history_dim=None, constraint: StressStrainConstraint = None,
-                 name: str = "user_law", tangent: str = "explicit"):
+                 name: str = "user_law", tangent: str = "explicit", *, _rotate=None):
         if not isinstance(tangent, str) or tangent not in TANGENT_MODES:
             raise ValueError(f"UserLaw: tangent={tangent!r}; expected one of {TANGENT_MODES}")
         self.tangent_mode = tangent
@@ -367,22 +385,25 @@ class UserLaw(IncrSmallStrainModel):
         self._history_dim = history_dim
         self._hist = [(n, _dim_value(n, d)) for n, d in hist]
         self.source = source
+        # objective.JaumannRate: ((history field, offset), ...) of the Mandel blocks rotated with the stress before the law runs
+        self._rotate = None if _rotate is None else tuple((str(f), int(o)) for f, o in _rotate)
+        rot_files = () if self._rotate is None else _ROTATION_FILES
         self._directions = None
         if tangent == "explicit":
             # cut for 4 waves per SIMD (128 VGPRs; the LDS allows no more); a law that spills there is compiled again for fewer waves
             for waves in WAVES_PER_SIMD:
-                self._compiled = _compile(self._program(source, waves), self.name)
+                self._compiled = _compile(self._program(source, waves), self.name, rot_files)
                 if not self._compiled.resources.get("scratch_bytes"):
                     break
             self._compiled_stress = self._compiled
         else:
             # two code objects: the stress-only kernel (T = double) for tangent=None launches, the tangent kernel (Dual<K>)
             for waves in WAVES_PER_SIMD:
-                self._compiled_stress = _compile(self._program_ad(source, waves, 0), self.name, _AD_FILES)
+                self._compiled_stress = _compile(self._program_ad(source, waves, 0), self.name, _AD_FILES + rot_files)
                 if not self._compiled_stress.resources.get("scratch_bytes"):
                     break
             for waves, k in AD_LADDER:
-                self._compiled = _compile(self._program_ad(source, waves, k), self.name, _AD_FILES)
+                self._compiled = _compile(self._program_ad(source, waves, k), self.name, _AD_FILES + rot_files)
                 self._directions = k
                 if not self._compiled.resources.get("scratch_bytes"):
                     break
@@ -395,8 +416,15 @@ class UserLaw(IncrSmallStrainModel):
         self._args_cls = _args_type(max(1, len(self._hist)))
 
     # -- program --------------------------------------------------------------------------------------------------------
+    def _rotation_lines(self) -> list:
+        """the generated block list and rotation.h (a law with ``_rotate``; none otherwise)"""
+        if self._rotate is None:
+            return []
+        return ["#define FCAMD_USER_ROTATE(X) " + " ".join(f"X({f}, {o})" for f, o in self._rotate), '#include "rotation.h"']
+
     def _program(self, source: str, waves: int) -> str:
-        """the generated definitions, the user's source, the template"""
+        """the generated definitions, the user's source, the template.  A rotated law renames the user's point function and
+        calls it from a generated one that first rotates the committed state (its gradient is an argument already)"""
         p = self._param_names
         lines = ['#include "user_law_api.h"',
                  f"#define FCAMD_USER_WAVES {waves}",
@@ -409,7 +437,10 @@ class UserLaw(IncrSmallStrainModel):
                  "    return p;",
                  "}",
                  '#line 1 "' + re.sub(r'[^A-Za-z0-9_.]', '_', self.name) + '"']
-        return "\n".join(lines) + "\n" + source + '\n#include "user_law.hip"\n'
+        if self._rotate is None:
+            return "\n".join(lines) + "\n" + source + '\n#include "user_law.hip"\n'
+        lines[-1:-1] = self._rotation_lines() + ["#define fcamd_user_point fcamd_user_point_unrotated"]
+        return "\n".join(lines) + "\n" + source + "\n" + _ROTATED_POINT + '#include "user_law.hip"\n'
 
     def _program_ad(self, source: str, waves: int, directions: int) -> str:
         """autodiff mode: the generated definitions, the user's template, the autodiff kernel template (``directions``: partials
@@ -427,6 +458,7 @@ class UserLaw(IncrSmallStrainModel):
                  "    return p;",
                  "}",
                  '#line 1 "' + re.sub(r'[^A-Za-z0-9_.]', '_', self.name) + '"']
+        lines[-1:-1] = self._rotation_lines()  # (user_law_ad.hip calls fcamd_user_rotate when FCAMD_USER_ROTATE is defined)
         return "\n".join(lines) + "\n" + source + '\n#include "user_law_ad.hip"\n'
 
     @property
@@ -607,6 +639,16 @@ class UserLaw(IncrSmallStrainModel):
 
         return int(to_host(c)[0])
 
+
+# the point function of a rotated explicit law: rotation.h's fcamd_user_rotate, then the user's (renamed) function
+_ROTATED_POINT = """#undef fcamd_user_point
+#line 1 "fcamd_objective_rate"
+__device__ __forceinline__ int fcamd_user_point(const UserParams& p, double t, double del_t, const double (&grad)[9],
+                                                const double (&eps)[6], double (&sigma)[6], double (&D)[36], UserHistory& h) {
+    fcamd_user_rotate(grad, sigma, h);
+    return fcamd_user_point_unrotated(p, t, del_t, grad, eps, sigma, D, h);
+}
+"""
 
 _num_cu_cache: dict = {}
 

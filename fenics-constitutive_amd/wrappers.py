@@ -40,6 +40,10 @@ class _From3D(IncrSmallStrainModel):
     fused = True
 
     def __init__(self, model: IncrSmallStrainModel) -> None:
+        from .objective import JaumannRate
+
+        if isinstance(model, JaumannRate):
+            JaumannRate._refuse(f"{type(self).__name__} (the 2-D / 1-D wrappers)")
         assert model.constraint.name == "FULL"
         if getattr(model, "field_points", None) is not None:
             raise NotImplementedError(f"{type(self).__name__}: laws with per-point parameter fields are not supported")
