@@ -8,7 +8,7 @@
 // shear entries by r and multiplying them back does not round-trip).  A point whose spin is exactly zero is left as it is:
 // hughes_winget returns false and nothing is rotated, so a symmetric G gives the unrotated law bit for bit.
 //
-// Used by the user-law templates (userlaw.py) behind the generated list
+// Used by the tile prologue of the user-law templates (user_law_tile.h, both tangent modes) behind the generated list
 //   FCAMD_USER_ROTATE(X)   X(history field, offset) for every rotated Mandel block of the history
 // and by the array-level kernel rotate_state.hip.  Compiled with -ffp-contract=off, like every program of the package.
 #pragma once

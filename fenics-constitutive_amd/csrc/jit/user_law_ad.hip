@@ -1,7 +1,6 @@
-// Kernel template of user laws in autodiff mode (userlaw.py, tangent="autodiff"): the memory side of user_law.hip around the
-// user's fcamd_user_stress<T> (user_law_ad.h).  Read at run time and compiled with hiprtc behind the generated definitions of
-// user_law.hip (FCAMD_USER_WAVES, FCAMD_USER_NHIST, FCAMD_USER_HISTORY_FIELDS, UserParams, fcamd_user_params), the template
-// UserHistoryT<T> and
+// Kernel template of user laws in autodiff mode (userlaw.py, tangent="autodiff"): the point step around the user's
+// fcamd_user_stress<T> (user_law_ad.h), inside the tile code of user_law_tile.h.  Compiled behind the generated definitions that
+// user_law_tile.h lists, the template UserHistoryT<T> (the committed history is read as UserHistoryT<double>) and
 //   FCAMD_USER_AD_K     0: the stress-only kernel (T = double, one pass); K > 0: the tangent kernel, ceil(6 / K) passes of
 //                       T = Dual<K>, pass c seeding the strain columns [c K, c K + K)
 //
@@ -11,90 +10,12 @@
 // every pass writes its own 6 K columns (user_columns_out): no 6x6 D is kept in registers.  Define FCAMD_USER_AD_DEBUG to check
 // that every pass computes the first pass's stress and return code; a point where they differ counts as not converged.
 #pragma once
+#include "user_law_tile.h"
 
 namespace fcamd_user {
-using namespace fcamd;
 
-constexpr int kMaxParams = 32;
-constexpr int kNH = FCAMD_USER_NHIST > 0 ? FCAMD_USER_NHIST : 1;
-constexpr int kUserWide = 18;
-constexpr int kUserRegion = kWave * kUserWide;
-constexpr int kUserMaxDim = 2 * kUserWide;
 constexpr int kK = FCAMD_USER_AD_K;
 constexpr int kPasses = kK > 0 ? (6 + kK - 1) / kK : 1;
-
-// the only kernel parameter: the layout of user_law.hip's UserArgs (userlaw.py: _args_type)
-struct UserArgs {
-    const double* grad;
-    const double* stress_in;
-    double* stress_out;
-    double* tangent;             // [36 n]; nullptr only in the stress-only kernel
-    const double* h_in[kNH];
-    double* h_out[kNH];
-    unsigned long long* nonconv;
-    long long n;
-    double t, del_t;
-    double factor;
-    double params[kMaxParams];
-};
-
-template <int NC>
-__device__ __forceinline__ void user_in(const Chunks<NC>& c, double* region, int lane, double (&x)[NC]) {
-    static_assert(NC <= kUserMaxDim, "history field wider than the LDS region");
-    if constexpr (NC <= kUserWide) {
-        transpose_in<NC>(c, region, lane, x);
-    } else {
-        constexpr int kHalf = 16 * NC;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-#pragma unroll
-            for (int k = 0; k < Chunks<NC>::K; ++k) {
-                const int q = k * kWave + lane - h * kHalf;
-                if (q >= 0 && q < kHalf && chunk_live<NC>(k, lane)) reinterpret_cast<d2*>(region)[q] = c.v[k];
-            }
-            wave_sync();
-            if ((lane >> 5) == h) {
-#pragma unroll
-                for (int i = 0; i < NC; ++i) x[i] = region[(lane & 31) * NC + i];
-            }
-            wave_sync();
-        }
-    }
-}
-
-template <int NC, bool FULL, bool NT>
-__device__ __forceinline__ void user_out(const double (&x)[NC], double* region, int lane, double* dst, int nelem) {
-    static_assert(NC <= kUserMaxDim, "history field wider than the LDS region");
-    if constexpr (NC <= kUserWide) {
-        transpose_out<NC, FULL, NT>(x, region, lane, dst, nelem);
-    } else {
-        constexpr int kHalf = 16 * NC;
-        constexpr int kPer = (kHalf + kWave - 1) / kWave;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            if ((lane >> 5) == h) {
-#pragma unroll
-                for (int i = 0; i < NC; ++i) region[(lane & 31) * NC + i] = x[i];
-            }
-            wave_sync();
-#pragma unroll
-            for (int k = 0; k < kPer; ++k) {
-                const int q = k * kWave + lane;
-                if (q < kHalf) {
-                    const d2 v = reinterpret_cast<const d2*>(region)[q];
-                    const int e = 2 * (q + h * kHalf);
-                    if constexpr (FULL) {
-                        store16<NT>(dst + e, v);
-                    } else {
-                        if (e < nelem) dst[e] = v.x;
-                        if (e + 1 < nelem) dst[e + 1] = v.y;
-                    }
-                }
-            }
-            wave_sync();
-        }
-    }
-}
 
 // the values of a history / stress array of Duals (or doubles)
 template <int NC, class T>
@@ -144,30 +65,12 @@ __device__ __forceinline__ void user_columns_out(const UserArgs& a, const Dual<K
     wave_sync();
 }
 
-// one 64-point tile (FULL) or the ragged last one (npts < 64); returns the tile's non-converged points (wave-uniform)
 template <bool FULL, bool NT>
 __device__ __forceinline__ unsigned long long user_tile(const UserArgs& a, const UserParams& p, double* region, long long p0,
                                                         int npts, int lane) {
-    Chunks<9> cg;
-    Chunks<6> cs;
-    tile_load<9, FULL, NT>(cg, a.grad + p0 * 9, npts * 9, lane);
-    tile_load<6, FULL, NT>(cs, a.stress_in + p0 * 6, npts * 6, lane);
-#define FCAMD_X(k, name, dim) \
-    Chunks<dim> c_##name;     \
-    tile_load<dim, FULL, NT>(c_##name, a.h_in[k] + p0 * (dim), npts * (dim), lane);
-    FCAMD_USER_HISTORY_FIELDS(FCAMD_X)
-#undef FCAMD_X
     double g[9], s[6], e[6];
     UserHistoryT<double> h;
-    transpose_in<9>(cg, region, lane, g);
-    transpose_in<6>(cs, region, lane, s);
-#define FCAMD_X(k, name, dim) user_in<dim>(c_##name, region, lane, h.name);
-    FCAMD_USER_HISTORY_FIELDS(FCAMD_X)
-#undef FCAMD_X
-#ifdef FCAMD_USER_ROTATE
-    fcamd_user_rotate(g, s, h);  // objective rate (rotation.h): the double committed state, before any Dual is seeded
-#endif
-    mandel_strain(g, a.factor, e);
+    user_tile_in<FULL, NT>(a, region, p0, npts, lane, g, s, e, h);
     const bool live = FULL || lane < npts;
     if constexpr (kK == 0) {
         const int rc = fcamd_user_stress<double>(p, a.t, a.del_t, e, s, h);
@@ -228,19 +131,3 @@ __device__ __forceinline__ unsigned long long user_tile(const UserArgs& a, const
 }
 
 }  // namespace fcamd_user
-
-extern "C" __global__ void __launch_bounds__(fcamd::kBlock, FCAMD_USER_WAVES) fcamd_user_law_kernel(const fcamd_user::UserArgs a) {
-    using namespace fcamd_user;
-    __shared__ __attribute__((aligned(16))) double scratch[kWavesPerBlock][kUserRegion];
-    const int lane = (int)threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave);
-    double* region = scratch[wave];
-    const UserParams p = fcamd_user_params(a.params);
-    const long long nfull = a.n / kWave;
-    const long long wstride = (long long)gridDim.x * kWavesPerBlock;
-    unsigned long long bad = 0;
-    long long tile = (long long)blockIdx.x * kWavesPerBlock + wave;
-    for (; tile < nfull; tile += wstride) bad += user_tile<true, true>(a, p, region, tile * kWave, kWave, lane);
-    if (tile == nfull && a.n > nfull * kWave) bad += user_tile<false, false>(a, p, region, tile * kWave, (int)(a.n - tile * kWave), lane);
-    if (bad != 0 && lane == 0) atomicAdd(a.nonconv, bad);
-}

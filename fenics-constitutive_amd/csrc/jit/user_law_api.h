@@ -1,6 +1,6 @@
 // The point-function contract of user-defined laws (fenics_constitutive_amd.UserLaw, userlaw.py).  Compiled at run time with
 // hiprtc for gfx950, together with the structs generated from the law's Python dicts, the user's source and the kernel template
-// user_law.hip, which does all the memory work.  The user writes ONE function:
+// user_law.hip, whose tile code (user_law_tile.h) does all the memory work.  The user writes ONE function:
 //
 //   struct UserParams  { double E, nu; };                             // generated: one double per parameter, in the given order
 //   struct UserHistory { double eps_p[6]; double alpha[1]; };          // generated: one array per history field (tuple: product)

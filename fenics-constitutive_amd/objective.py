@@ -20,15 +20,14 @@ from __future__ import annotations
 
 import ctypes as C
 
-from . import _capi, userlaw
-from .device import _check_numpy, _check_torch, _current_stream_ptr, _is_torch, _size
-from .interfaces import IncrSmallStrainModel, StressStrainConstraint
+from . import jit
+from .device import _check_torch, _is_torch
+from .interfaces import StressStrainConstraint
 from .userlaw import UserLaw
 
 __all__ = ["JaumannRate", "default_rotatable"]
 
 ROTATE_KERNEL = "fcamd_rotate_state_kernel"
-_ROTATE_FILES = ("rotation.h", "rotate_state.hip")
 
 
 def default_rotatable(model) -> dict:
@@ -83,8 +82,8 @@ def _fused_law(model, blocks):
     from . import userlaw_sources as S
 
     if isinstance(model, UserLaw):
-        return UserLaw(model.source, list(zip(model._param_names, model._param_values)), model._history_dim, model.constraint,
-                       name=model.name, tangent=model.tangent_mode, _rotate=blocks)
+        return UserLaw(model.source, model.parameters, model.history_dim, model.constraint, name=model.name,
+                       tangent=model.tangent_mode, _rotate=blocks)
     if getattr(model, "field_points", None) is not None:
         return None
     if type(model) is M.LinearElasticityModel:
@@ -102,7 +101,7 @@ def _fused_law(model, blocks):
     return UserLaw(src, p, hist, StressStrainConstraint.FULL, name=name, _rotate=blocks)
 
 
-class JaumannRate(IncrSmallStrainModel):
+class JaumannRate(jit.JitLaw):
     """A FULL ``IncrSmallStrainModel`` of this package whose committed state is rotated with the material before every
     evaluation (Jaumann rate, Hughes-Winget rotation; module docstring).
 
@@ -142,7 +141,8 @@ class JaumannRate(IncrSmallStrainModel):
         for name, off in self._blocks:
             self.rotatable.setdefault(name, []).append(off)
         self._fused = _fused_law(model, self._blocks)
-        self._rot_fields = [(name, dim) for name, dim in _history_dims(model) if any(b[0] == name for b in self._blocks)]
+        self._hist = _history_dims(model)
+        self._rot_fields = [(name, dim) for name, dim in self._hist if any(b[0] == name for b in self._blocks)]
         self._rot = None  # the standalone rotation kernel, compiled on first use
         self._last = model  # the law that ran last (device_stats)
 
@@ -178,31 +178,12 @@ class JaumannRate(IncrSmallStrainModel):
     def update(self) -> None:
         self.model.update()
 
-    def use_devices(self, devices):
-        self._refuse("use_devices (several GPUs in one process)")
-
-    def evaluate_indexed(self, *args, **kwargs):
-        self._refuse("evaluate_indexed (parent rows)")
-
-    @staticmethod
-    def _refuse_batched():
-        if getattr(_capi._tls, "batch", None) is not None:
-            JaumannRate._refuse("a call inside batched_launches()")
-
     def device_stats(self, device: int = 0):
         """``device_stats`` of the law that ran last on the call's behalf (the fused UserLaw returns its count, a built-in law
         raises on non-convergence)"""
         return self._last.device_stats(device)
 
     # -- evaluate ---------------------------------------------------------------------------------------------------------
-    def _hist(self, history) -> list:
-        dims = _history_dims(self.model)
-        if not dims:
-            return []
-        if history is None:
-            raise ValueError("history must not be None")
-        return [history[name] for name, _ in dims]
-
     def _spring_checks(self, del_t) -> None:
         from .models import _SpringBase
 
@@ -218,13 +199,13 @@ class JaumannRate(IncrSmallStrainModel):
             self._fused.evaluate(t, del_t, grad_del_u, stress, tangent, history, check=check)
             return
         self._last = self.model
-        hist = self._hist(history)
-        n = self._check_sizes(grad_del_u, stress, tangent, hist)
+        hist = self._history_arrays(history)
+        n = self._sizes(grad_del_u, stress, tangent, hist)
         if _is_torch(grad_del_u):
             self._rotate(n, grad_del_u, stress, stress, hist, hist)
             self.model.evaluate(t, del_t, grad_del_u, stress, tangent, history, check=check)
             return
-        self._evaluate_host(t, del_t, n, grad_del_u, stress, tangent, history, hist)
+        self._evaluate_host(t, del_t, n, grad_del_u, stress, tangent, hist)
 
     def evaluate_from(self, t, del_t, grad_del_u, stress_prev, stress, tangent, history_prev, history) -> None:
         """Out-of-place device evaluate: reads the committed state (``stress_prev``, ``history_prev``, never written), rotates
@@ -238,60 +219,23 @@ class JaumannRate(IncrSmallStrainModel):
             self._fused.evaluate_from(t, del_t, grad_del_u, stress_prev, stress, tangent, history_prev, history)
             return
         self._last = self.model
-        hist, hprev = self._hist(history), self._hist(history_prev)
-        n = self._check_sizes(grad_del_u, stress, tangent, hist)
-        assert _size(stress_prev) == 6 * n, "Stress, strain, and tangent lengths do not match"
-        for (name, dim), h in zip(_history_dims(self.model), hprev):
-            assert _size(h) == n * dim, f"history '{name}' has the wrong length"
+        hist, hprev = self._history_arrays(history), self._history_arrays(history_prev)
+        n = self._sizes(grad_del_u, stress, tangent, hist, stress_prev, hprev)
         rotated = {name for name, _ in self._rot_fields}
-        for (name, _), hp, h in zip(_history_dims(self.model), hprev, hist):
+        for (name, _), hp, h in zip(self._hist, hprev, hist):
             if name not in rotated:  # the rotation kernel writes the rotated fields; the rest is the committed state as it is
                 _check_torch(f"history['{name}']", h).copy_(_check_torch(f"history_prev['{name}']", hp))
-        self._rotate(n, grad_del_u, stress_prev, stress, hprev, hist)
-        self.model.evaluate(t, del_t, grad_del_u, stress, tangent, history)
+        self._evaluate_device(t, del_t, n, grad_del_u, stress_prev, stress, tangent, hprev, hist)
 
-    def _check_sizes(self, grad, stress, tangent, hist) -> int:
-        n = _size(grad) // 9
-        assert n == _size(stress) // 6 and (tangent is None or n == _size(tangent) // 36), "Stress, strain, and tangent lengths do not match"
-        assert _size(grad) == n * 9 and _size(stress) == n * 6, "Input arrays are not of the correct length"
-        for (name, dim), h in zip(_history_dims(self.model), hist):
-            assert _size(h) == n * dim, f"history '{name}' has the wrong length"
-        return n
+    def _evaluate_device(self, t, del_t, n, grad, stress_prev, stress, tangent, hist_prev, hist) -> None:
+        """the array-level path on device tensors: the rotated committed state into ``stress`` and the rotated fields of
+        ``hist`` (the others hold the committed state already), then the law evaluates there in place"""
+        self._rotate(n, grad, stress_prev, stress, hist_prev, hist)
+        self.model.evaluate(t, del_t, grad, stress, tangent, {name: h for (name, _), h in zip(self._hist, hist)})
 
-    def _evaluate_host(self, t, del_t, n, grad, stress, tangent, history, hist) -> None:
-        """NumPy arrays: staged through device copies (as the *From3D wrappers do), rotated and evaluated there, back in
-        place; non-convergence raises after the results are written"""
-        import numpy as np
-        import torch
-
-        from .hostio import assign, to_device
-
-        _check_numpy("grad_del_u", grad)
-        _check_numpy("stress", stress)
-        if tangent is not None:
-            _check_numpy("tangent", tangent)
-        for (name, _), h in zip(_history_dims(self.model), hist):
-            _check_numpy(f"history['{name}']", h)
-        if n == 0:
-            return
-        dev = _capi.default_device()
-        d = torch.device("cuda", dev)
-        with torch.cuda.device(d):
-            g = to_device(grad.reshape(-1), d, np.float64)
-            s = to_device(stress.reshape(-1), d, np.float64)
-            tan = None if tangent is None else torch.empty(36 * n, dtype=torch.float64, device=d)
-            hd = [to_device(h.reshape(-1), d, np.float64) for h in hist]
-            h_dev = None if history is None else dict(zip([name for name, _ in _history_dims(self.model)], hd))
-            self._rotate(n, g, s, s, hd, hd)
-            self.model.evaluate(t, del_t, g, s, tan, h_dev)
-            assign(stress.reshape(-1), s)
-            if tangent is not None:
-                assign(tangent.reshape(-1), tan)
-            for h, x in zip(hist, hd):
-                assign(h.reshape(-1), x)
-            count = self.model.device_stats(dev)  # a built-in law raises here
-            if isinstance(self.model, UserLaw):
-                UserLaw._raise(count)
+    def _nonconverged(self, device: int) -> int:
+        count = self.model.device_stats(device)  # a built-in law raises here
+        return count if isinstance(self.model, UserLaw) else 0
 
     # -- the standalone rotation kernel ---------------------------------------------------------------------------------
     def _rotate_kernel(self):
@@ -302,7 +246,7 @@ class JaumannRate(IncrSmallStrainModel):
                      "#define FCAMD_USER_ROTATE(X) " + " ".join(f"X({names[n]}, {o})" for n, o in self._blocks),
                      "struct RotHistory {" + "".join(f" double {names[n]}[{d}];" for n, d in self._rot_fields) + " };",
                      '#include "rotate_state.hip"']
-            self._rot = userlaw._compile("\n".join(lines) + "\n", "jaumann_rotate_state", _ROTATE_FILES, ROTATE_KERNEL)
+            self._rot = jit.compile_program("\n".join(lines) + "\n", "jaumann_rotate_state", ROTATE_KERNEL)
             if self._rot.resources.get("scratch_bytes"):
                 raise RuntimeError(f"JaumannRate: the rotation kernel uses {self._rot.resources['scratch_bytes']} bytes of scratch")
         return self._rot
@@ -310,10 +254,8 @@ class JaumannRate(IncrSmallStrainModel):
     def _rotate(self, n, grad, stress_in, stress_out, hist_in, hist_out) -> None:
         """the rotated committed state -> ``stress_out`` and the rotated history fields of ``hist_out`` (asynchronous, on torch's
         current stream)"""
-        import torch
-
         rotated = {name for name, _ in self._rot_fields}
-        pairs = [(hi, ho) for (name, _), hi, ho in zip(_history_dims(self.model), hist_in, hist_out) if name in rotated]
+        pairs = [(hi, ho) for (name, _), hi, ho in zip(self._hist, hist_in, hist_out) if name in rotated]
         dev = grad.device.index or 0
         for label, a in [("grad_del_u", grad), ("stress_prev", stress_in), ("stress", stress_out)] + \
                 [("history", x) for p in pairs for x in p]:
@@ -322,18 +264,12 @@ class JaumannRate(IncrSmallStrainModel):
                 raise ValueError(f"{label} is on {a.device}, grad_del_u on cuda:{dev}")
         if n == 0:
             return
-        fn = self._rotate_kernel().function(dev)
         a = _rotate_args_type(max(1, len(pairs)))()
         a.grad, a.s_in, a.s_out = grad.data_ptr(), stress_in.data_ptr(), stress_out.data_ptr()
         for k, (hi, ho) in enumerate(pairs):
             a.h_in[k], a.h_out[k] = hi.data_ptr(), ho.data_ptr()
         a.n = n
-        blocks = min((n + 255) // 256, 64 * userlaw._num_cu(dev))
-        params = (C.c_void_p * 1)(C.cast(C.pointer(a), C.c_void_p))
-        hip = userlaw._load_hip()
-        with torch.cuda.device(dev):
-            userlaw._hip_check(hip.hipModuleLaunchKernel(fn, blocks, 1, 1, 256, 1, 1, 0, C.c_void_p(_current_stream_ptr(dev)),
-                                                         params, None), "JaumannRate rotation launch")
+        jit.launch(self._rotate_kernel(), dev, min((n + 255) // 256, 64 * jit.num_cu(dev)), a, "JaumannRate rotation launch")
 
 
 def _rotate_args_type(nf: int):

@@ -1,15 +1,16 @@
 """Objective-rate wrapper (fenics_constitutive_amd.JaumannRate), the parts that need no GPU: the NumPy Hughes-Winget oracle,
-the rotated programs compile for gfx950 without scratch, unrotated programs and cache keys are what they were, and the
-validation of ``rotatable`` and the refused forms."""
+the rotated programs compile for gfx950 without scratch, unrotated programs are what they were, the compile cache key
+follows every file a program includes, and the validation of ``rotatable`` and the refused forms."""
 
 import hashlib
 import os
+import shutil
 
 import numpy as np
 import pytest
 
 import fenics_constitutive_amd as fc
-from fenics_constitutive_amd import objective, userlaw, userlaw_sources as S
+from fenics_constitutive_amd import jit, objective, userlaw, userlaw_sources as S
 from objective_rate_util import hughes_winget, hughes_winget_closed, rotate, to_tensor
 
 FULL = fc.StressStrainConstraint.FULL
@@ -30,8 +31,6 @@ UNROTATED_PROGRAMS = {
     "spring_maxwell_ad": "4b0f206f78cbcb651c25522b97fec847d518db36942d28f8a4c12ceba588f9c3",
     "von_mises_3d_ad": "40d7de666aa32ab31fab3a47bad24289ad2f64cfbc0550ca7ce79681fe787530",
 }
-# sha256 of csrc/jit/user_law_ad.hip before it gained the rotation hook
-UNROTATED_AD_TEMPLATE = "172645ab3247b540a0b5ffd6679a5839bce244fc13fcee91058d22eeec96a388"
 
 
 # --- the NumPy oracle -----------------------------------------------------------------------------------------------------
@@ -124,25 +123,33 @@ def test_unrotated_programs_are_byte_identical(make, p):
     assert "ROTATE" not in prog and "rotation.h" not in prog
 
 
-def test_unrotated_autodiff_cache_key_ignores_the_hook():
-    with open(os.path.join(userlaw.JIT_DIR, "user_law_ad.hip")) as fh:
-        text = fh.read()
-    assert "#ifdef FCAMD_USER_ROTATE" in text
-    stripped = userlaw._key_text(os.path.join(userlaw.JIT_DIR, "user_law_ad.hip"), "no rotation here")
-    assert hashlib.sha256(stripped.encode()).hexdigest() == UNROTATED_AD_TEMPLATE
-    assert userlaw._key_text(os.path.join(userlaw.JIT_DIR, "user_law_ad.hip"), "#define FCAMD_USER_ROTATE(X)") == text
-    law = S.linear_elasticity_ad(LE_P)
-    program = law._program_ad(law.source, law.resources["waves_per_simd"], law.resources["directions_per_pass"])
-
-    def read(*parts):
-        with open(os.path.join(*parts)) as fh:
-            return fh.read()
-
-    h = hashlib.sha256()
-    for part in (read(userlaw.JIT_DIR, "user_law.hip"), read(userlaw.JIT_DIR, "user_law_api.h"), read(userlaw.KERNEL_DIR, "tile_io.h"),
-                 read(userlaw.JIT_DIR, "user_law_ad.h"), stripped, program, " ".join(userlaw.OPTIONS), userlaw._rtc_version()):
-        h.update(part.encode() + b"\0")
-    assert law._compiled.key == h.hexdigest()
+def test_cache_key_changes_with_every_included_file(tmp_path, monkeypatch):
+    """in a copy of the source tree, one changed byte in any file of a rotated autodiff law's include closure changes the key;
+    a file outside the closure does not"""
+    fused = fc.JaumannRate(S.linear_elasticity_ad(LE_P))._fused
+    program = fused._program_ad(fused.source, 4, 6)
+    csrc = tmp_path / "csrc"
+    shutil.copytree(os.path.dirname(jit.JIT_DIR), csrc)
+    monkeypatch.setattr(jit, "INCLUDE_DIRS", (str(csrc / "jit"), str(csrc / "kernels")))
+    key = jit.cache_key(program)
+    assert key == fused._compiled.key  # the copy holds the same text
+    files = jit.include_closure(program)
+    assert {os.path.relpath(f, csrc) for f in files} == {
+        "jit/user_law_ad.h", "jit/user_law_api.h", "kernels/tile_io.h", "fcamd_internal.h", "kernels/param_source.h",
+        "jit/rotation.h", "jit/user_law_ad.hip", "jit/user_law_tile.h"}
+    for f in files:
+        with open(f, "rb") as fh:
+            data = fh.read()
+        with open(f, "wb") as fh:
+            fh.write(bytes([data[0] ^ 1]) + data[1:])
+        assert jit.cache_key(program) != key, f
+        with open(f, "wb") as fh:
+            fh.write(data)
+    assert jit.cache_key(program) == key
+    for other in ("jit/user_law.hip", "jit/rotate_state.hip", "kernels/law_sls.h"):
+        with open(csrc / other, "a") as fh:
+            fh.write(" ")
+    assert jit.cache_key(program) == key
 
 
 def test_wrapping_does_not_change_the_wrapped_law():

@@ -8,7 +8,7 @@ import os
 import pytest
 
 import fenics_constitutive_amd as fc
-from fenics_constitutive_amd import userlaw, userlaw_sources as S
+from fenics_constitutive_amd import jit, userlaw, userlaw_sources as S
 
 LE_P = {"E": 42.0, "nu": 0.3}
 SLS_P = {"E0": 42.0, "E1": 10.0, "tau": 10.0, "nu": 0.2}
@@ -83,21 +83,26 @@ def test_modes_do_not_share_cache_entries():
     assert userlaw.compile_count() == n and ad2._compiled is ad._compiled
 
 
-def test_explicit_cache_key_is_unchanged():
-    """the explicit mode's key is the hash of exactly what it was before autodiff mode existed"""
-    law = S.linear_elasticity(LE_P)
-    program = law._program(law.source, law.resources["waves_per_simd"])
+def test_cache_key_is_the_hash_of_the_include_closure():
+    """the key of either mode, recomputed from the program and the files it includes (found by following the #include lines);
+    the closure reaches the library headers that user_law_api.h and tile_io.h include"""
 
-    def read(*parts):
-        with open(os.path.join(*parts)) as fh:
+    def read(path):
+        with open(path) as fh:
             return fh.read()
 
-    h = hashlib.sha256()
-    for part in (read(userlaw.JIT_DIR, "user_law.hip"), read(userlaw.JIT_DIR, "user_law_api.h"),
-                 read(userlaw.KERNEL_DIR, "tile_io.h"), program, " ".join(userlaw.OPTIONS), userlaw._rtc_version()):
-        h.update(part.encode() + b"\0")
-    assert law._compiled.key == h.hexdigest()
-    assert "user_law_ad" not in program
+    csrc = os.path.dirname(jit.JIT_DIR)
+    common = {"jit/user_law_api.h", "jit/user_law_tile.h", "kernels/tile_io.h", "kernels/param_source.h", "fcamd_internal.h"}
+    ex, ad = S.linear_elasticity(LE_P), S.linear_elasticity_ad(LE_P)
+    for law, program, own in [(ex, ex._program(ex.source, 4), {"jit/user_law.hip"}),
+                              (ad, ad._program_ad(ad.source, 4, 6), {"jit/user_law_ad.h", "jit/user_law_ad.hip"})]:
+        files = jit.include_closure(program)
+        assert {os.path.relpath(f, csrc) for f in files} == common | own
+        h = hashlib.sha256()
+        for part in (program, " ".join(jit.OPTIONS), jit.rtc_version(), *jit._STUB_HEADERS.values(), *map(read, files)):
+            h.update(part.encode() + b"\0")
+        assert law._compiled.key == h.hexdigest()
+    assert "user_law_ad" not in ex._program(ex.source, 4)
 
 
 def test_autodiff_program_text():
