@@ -202,6 +202,7 @@ class JaumannRate(jit.JitLaw):
         hist = self._history_arrays(history)
         n = self._sizes(grad_del_u, stress, tangent, hist)
         if _is_torch(grad_del_u):
+            self._check_call(grad_del_u, stress, stress, tangent, hist, hist)
             self._rotate(n, grad_del_u, stress, stress, hist, hist)
             self.model.evaluate(t, del_t, grad_del_u, stress, tangent, history, check=check)
             return
@@ -221,11 +222,33 @@ class JaumannRate(jit.JitLaw):
         self._last = self.model
         hist, hprev = self._history_arrays(history), self._history_arrays(history_prev)
         n = self._sizes(grad_del_u, stress, tangent, hist, stress_prev, hprev)
+        self._check_call(grad_del_u, stress_prev, stress, tangent, hprev, hist)
         rotated = {name for name, _ in self._rot_fields}
         for (name, _), hp, h in zip(self._hist, hprev, hist):
             if name not in rotated:  # the rotation kernel writes the rotated fields; the rest is the committed state as it is
                 _check_torch(f"history['{name}']", h).copy_(_check_torch(f"history_prev['{name}']", hp))
         self._evaluate_device(t, del_t, n, grad_del_u, stress_prev, stress, tangent, hprev, hist)
+
+    def _check_call(self, grad, stress_prev, stress, tangent, hist_prev, hist) -> None:
+        """the array-level path on device tensors: what the wrapped law will refuse (``UserLaw._check_device_arrays``;
+        ``DeviceLaw._evaluate_device`` and ``check_device_ex`` of fcamd_capi.cpp), with its error, before the rotation kernel
+        writes the rotated state over the committed one (in place) or into the trial arrays.  The rotation kernel itself moves
+        8-byte words and needs no alignment; the laws' kernels move 16-byte chunks."""
+        if isinstance(self.model, UserLaw):
+            self.model._check_device_arrays(grad, stress_prev, stress, tangent, hist_prev, hist)
+            return
+        from . import _capi
+
+        arrays = [("grad_del_u", grad), ("stress", stress)] + ([] if tangent is None else [("tangent", tangent)])
+        arrays += [(f"history['{name}']", h) for (name, _), h in zip(self._hist, hist)]
+        if stress_prev is not stress:
+            arrays += [("stress_prev", stress_prev)] + [("history_prev", h) for h in hist_prev]
+        for label, a in arrays:
+            _check_torch(label, a)
+        if any(a.data_ptr() % 16 for label, a in arrays if not label.startswith("history")):
+            raise ValueError(_capi.status_string(_capi.ERR_ALIGN))
+        if any(a.data_ptr() % 16 for label, a in arrays if label.startswith("history")):
+            raise ValueError("device history arrays must be 16-byte aligned")
 
     def _evaluate_device(self, t, del_t, n, grad, stress_prev, stress, tangent, hist_prev, hist) -> None:
         """the array-level path on device tensors: the rotated committed state into ``stress`` and the rotated fields of

@@ -256,7 +256,9 @@ class UserLaw(jit.JitLaw):
             c = self._counters[device] = torch.zeros(1, dtype=torch.int64, device=torch.device("cuda", device))
         return c
 
-    def _evaluate_device(self, t, del_t, n, grad, stress_prev, stress, tangent, hist_prev, hist) -> None:
+    def _check_device_arrays(self, grad, stress_prev, stress, tangent, hist_prev, hist) -> int:
+        """every tensor of a call is float64, contiguous, on grad_del_u's device (returned) and 16-byte aligned: the tile code
+        moves 16-byte chunks.  Raises before anything is launched (objective.JaumannRate: before anything is rotated)."""
         arrays = [("grad_del_u", grad), ("stress_prev", stress_prev), ("stress", stress)]
         if tangent is not None:
             arrays.append(("tangent", tangent))
@@ -269,6 +271,10 @@ class UserLaw(jit.JitLaw):
                 raise ValueError(f"{label} is on {a.device}, grad_del_u on cuda:{dev}")
             if a.data_ptr() % 16:
                 raise ValueError(f"{label}: device arrays must be 16-byte aligned")
+        return dev
+
+    def _evaluate_device(self, t, del_t, n, grad, stress_prev, stress, tangent, hist_prev, hist) -> None:
+        dev = self._check_device_arrays(grad, stress_prev, stress, tangent, hist_prev, hist)
         self._empty[dev] = n == 0
         if n == 0:  # nothing is launched (device_stats: 0)
             return
