@@ -237,6 +237,16 @@ void pool_begin(ExpandPool* p, const HostTangentJob& job);
 int pool_post(ExpandPool* p, int64_t p0, int64_t np, const double* src, const unsigned long long* mask);  // -> ticket
 // doubles of one ring slot for chunks of `chunk` points (a multiple of 64): 8 per point + one ballot word per tile
 inline size_t host_tangent_slot_doubles(int64_t chunk, int prm) { return (size_t)chunk * (size_t)prm + (((size_t)chunk / 64 + 1) & ~(size_t)1); }  // (slots stay 16-byte aligned)
+// The chunks of the parameter pipeline for a call of n points (option "host_tangent_chunk": opt_chunk, 0 = automatic): chunk k is
+// points [start[k], start[k + 1]), every start a multiple of 64, none longer than `chunk` (a multiple of 64, the size of a ring slot), the
+// tail cut in halves; `nslots` ring slots (4 .. kTangentSlots: what 256 MiB of page-locked memory hold).  Pure: fcamd_hostpath.cpp's
+// run_param_chunks follows it, the tests check it on its own.
+struct HostTangentPlan {
+    int64_t chunk;
+    int nslots;
+    std::vector<int64_t> start;  // nchunks + 1 entries, the last one n
+};
+HostTangentPlan host_tangent_plan(int64_t n, long long opt_chunk, int prm);
 void pool_wait(ExpandPool* p, int ticket);
 void pool_finish(ExpandPool* p);
 double pool_busy_seconds(ExpandPool* p);

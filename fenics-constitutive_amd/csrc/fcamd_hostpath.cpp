@@ -547,32 +547,13 @@ int run_const_tangent(fcamd_model* m, ExpandPool* pool, int64_t n, double* tange
 template <class Launch>
 int run_param_chunks(fcamd_model* m, ExpandPool* pool, int64_t n, double* tangent, fcamd_stats* stats, Launch&& launch) {
     fcamd_context* c = m->ctx;
-    // Chunks.  The GPU is the slower side of the pipeline (VonMises3D at 1e7 points: 33 ms on the link against 16 x 17 ms of expansion),
-    // so a call takes the kernels' time plus the expansion of the LAST chunk (2.3 ns per point of it) plus what the chunk boundaries cost:
-    // a kernel's last waves drain over the link before the next kernel of the stream may start -- ~150 us per boundary at 1e7 points
-    // (38 chunks of 256 Ki points 37.7 ms, 10 of 1 Mi 33.4 ms, same run-ahead), nothing measurable at 1e6 (chunks of 64 Ki / 128 Ki /
-    // 256 Ki points: 4.02 / 4.17 / 4.28 ms: there the tail decides).  So: a twelfth of the call, 64 Ki .. 1 Mi points, the last chunk cut
-    // in halves down to 64 Ki points; and as many ring slots as 256 MiB of page-locked memory hold (4 .. 16): the GPU runs that far
-    // ahead of the expansion when a thread of the pool is held up by another tenant of the host.
-    int64_t chunk = c->opt.host_tangent_chunk > 0 ? c->opt.host_tangent_chunk : std::max<int64_t>(1 << 16, std::min<int64_t>(1 << 20, (n / 12 + 63) / 64 * 64));
-    chunk = std::max<int64_t>(64, chunk / 64 * 64);
-    chunk = std::min<int64_t>(chunk, (n + 63) / 64 * 64);
-    std::vector<int64_t> start;  // chunk k = points [start[k], start[k + 1])
-    {
-        const int64_t taper_min = c->opt.host_tangent_chunk > 0 ? chunk : (1 << 16);
-        int64_t p = 0;
-        while (p < n) {
-            start.push_back(p);
-            const int64_t left = n - p;
-            int64_t take = chunk;
-            if (left <= chunk) take = left > 2 * taper_min ? (left / 2 + 63) / 64 * 64 : left;  // the tail: halves down to taper_min
-            p += std::min(take, left);
-        }
-        start.push_back(n);
-    }
+    // the chunks, their tapered tail and the ring's slots: host_tangent_plan
     const HostTangentJob job = host_tangent_job(m, tangent);
     const int prm = job.prm;
-    const int nslots = (int)std::max<int64_t>(4, std::min<int64_t>(fcamd_context::kTangentSlots, ((int64_t)256 << 20) / (chunk * prm * 8)));
+    const HostTangentPlan plan = host_tangent_plan(n, c->opt.host_tangent_chunk, prm);  // (fcamd_hosttangent.cpp)
+    const int64_t chunk = plan.chunk;
+    const std::vector<int64_t>& start = plan.start;  // chunk k = points [start[k], start[k + 1])
+    const int nslots = plan.nslots;
     int st = host_tangent_ring(c, chunk, nslots, prm);
     if (st != FCAMD_OK) return st;
     pool_begin(pool, job);

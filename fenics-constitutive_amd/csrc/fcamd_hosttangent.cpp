@@ -395,6 +395,36 @@ HostTangentJob host_tangent_job(const fcamd_model* m, double* tangent) {
     return j;
 }
 
+// Chunks.  The GPU is the slower side of the pipeline (VonMises3D at 1e7 points: 33 ms on the link against 16 x 17 ms of expansion),
+// so a call takes the kernels' time plus the expansion of the LAST chunk (2.3 ns per point of it) plus what the chunk boundaries cost:
+// a kernel's last waves drain over the link before the next kernel of the stream may start -- ~150 us per boundary at 1e7 points
+// (38 chunks of 256 Ki points 37.7 ms, 10 of 1 Mi 33.4 ms, same run-ahead), nothing measurable at 1e6 (chunks of 64 Ki / 128 Ki /
+// 256 Ki points: 4.02 / 4.17 / 4.28 ms: there the tail decides).  So: a twelfth of the call, 64 Ki .. 1 Mi points, the last chunk cut
+// in halves down to 64 Ki points; and as many ring slots as 256 MiB of page-locked memory hold (4 .. 16): the GPU runs that far
+// ahead of the expansion when a thread of the pool is held up by another tenant of the host.
+HostTangentPlan host_tangent_plan(int64_t n, long long opt_chunk, int prm) {
+    HostTangentPlan plan;
+    int64_t chunk = opt_chunk > 0 ? (int64_t)opt_chunk : std::max<int64_t>(1 << 16, std::min<int64_t>(1 << 20, (n / 12 + 63) / 64 * 64));
+    chunk = std::max<int64_t>(64, chunk / 64 * 64);
+    // the four slots the ring has at least stay within the 256 MiB too: 1 Mi points of 8 doubles, 699 008 of Drucker-Prager's 12 (the
+    // automatic plan of a Drucker-Prager call of more than 8.4e6 points and an option beyond it asked for a ring of 384 MiB and more)
+    chunk = std::min<int64_t>(chunk, ((int64_t)256 << 20) / (4 * (int64_t)prm * 8) / 64 * 64);
+    chunk = std::min<int64_t>(chunk, (n + 63) / 64 * 64);
+    const int64_t taper_min = opt_chunk > 0 ? chunk : (1 << 16);
+    int64_t p = 0;
+    while (p < n) {
+        plan.start.push_back(p);
+        const int64_t left = n - p;
+        int64_t take = chunk;
+        if (left <= chunk) take = left > 2 * taper_min ? (left / 2 + 63) / 64 * 64 : left;  // the tail: halves down to taper_min
+        p += std::min(take, left);
+    }
+    plan.start.push_back(n);
+    plan.chunk = chunk;
+    plan.nslots = (int)std::max<int64_t>(4, std::min<int64_t>(fcamd_context::kTangentSlots, ((int64_t)256 << 20) / (chunk * prm * 8)));
+    return plan;
+}
+
 // the ring of page-locked parameter chunks: `slots` x (`chunk` points x `prm` doubles + chunk / 64 ballot words), and one event per slot
 int host_tangent_ring(fcamd_context* c, int64_t chunk, int slots, int prm) {
     const size_t bytes = (size_t)slots * host_tangent_slot_doubles(chunk, prm) * sizeof(double);

@@ -130,6 +130,10 @@ def test_von_mises_values_bitwise_and_tangent(n):
     assert np.array_equal(s_ad, s_ex) and same_hist(h_ad, h_ex)
     assert np.count_nonzero(h_ad["alpha"] != h0["alpha"]) > 0  # some points were plastic
     assert rel_err(t_ad, t_ex) <= TOL["pl"], rel_err(t_ad, t_ex)
+    # the built-in call's stress and history too: a wrong built-in tangent with these right lies in the tangent path alone
+    assert rel_err(s_bi, s_ex) <= TOL["pl"], rel_err(s_bi, s_ex)
+    for k in h_ex:
+        assert rel_err(h_bi[k], h_ex[k]) <= TOL["pl"], (k, rel_err(h_bi[k], h_ex[k]))
     assert rel_err(t_ad, t_bi) <= TOL["pl"], rel_err(t_ad, t_bi)
 
 
