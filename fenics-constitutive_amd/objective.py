@@ -9,7 +9,7 @@ The math and its device code: ``csrc/jit/rotation.h``.
 Two paths:
 
 * fused: the rotation runs in registers inside the law's own kernel, between the transposition of the state and the point
-  function (no extra bytes per point).  For ``UserLaw`` (both tangent modes) and, through their ``userlaw_sources``
+  function (no extra bytes per point).  For ``UserLaw`` (every tangent mode) and, through their ``userlaw_sources``
   transcriptions, ``LinearElasticityModel`` (FULL), ``SpringMaxwellModel`` (FULL) and ``VonMises3D`` with scalar parameters.
 * array-level: every other FULL law of the package (``SpringKelvinModel``, the comfe-rs laws, laws with parameter fields).
   A standalone kernel (``csrc/jit/rotate_state.hip``) writes the rotated committed state into the arrays the law then
@@ -83,7 +83,7 @@ def _fused_law(model, blocks):
 
     if isinstance(model, UserLaw):
         return UserLaw(model.source, model.parameters, model.history_dim, model.constraint, name=model.name,
-                       tangent=model.tangent_mode, _rotate=blocks)
+                       tangent=model.tangent_mode, unknowns=model.unknowns, newton=model.newton, _rotate=blocks)
     if getattr(model, "field_points", None) is not None:
         return None
     if type(model) is M.LinearElasticityModel:

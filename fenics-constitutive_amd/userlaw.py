@@ -10,6 +10,10 @@ no GPU: the arch is fixed.
 With ``tangent="autodiff"`` the source defines a stress and history update templated on the scalar type, compiled inside
 ``csrc/jit/user_law_ad.hip``; the tangent comes from forward-mode automatic differentiation (``csrc/jit/user_law_ad.h``).
 
+With ``tangent="implicit"`` the source states the law as a residual in ``unknowns`` local unknowns and the state update from
+their solution (``csrc/jit/user_law_implicit.h``); the kernel template ``csrc/jit/user_law_implicit.hip`` brings the Jacobian (dual
+numbers), the per-point Newton loop, the dense solve and the consistent tangent by the implicit-function theorem.
+
 FULL constraint, scalar parameters, ``evaluate`` / ``evaluate_from``: the resident, batched, indexed and multi-GPU forms of the
 built-in laws are refused with ``NotImplementedError``.
 """
@@ -38,7 +42,12 @@ WAVES_PER_SIMD = (4, 3, 2)
 #: as 8-byte entries (SpringMaxwellModel: 2.09x the time of K = 6 at 3 instead of 2 waves); then the most waves
 #: with the fewest passes
 AD_LADDER = tuple((w, 6) for w in WAVES_PER_SIMD) + tuple((w, k) for w in WAVES_PER_SIMD for k in (3, 2, 1))
-TANGENT_MODES = ("explicit", "autodiff")
+TANGENT_MODES = ("explicit", "autodiff", "implicit")
+#: implicit laws: the most local unknowns (an 8 x 8 Jacobian and its right-hand sides stay in registers)
+MAX_UNKNOWNS = 8
+#: implicit laws: max_iter and tol travel in two slots of UserArgs.params behind the law's own parameters
+MAX_IMPLICIT_PARAMS = MAX_PARAMS - 2
+NEWTON_DEFAULTS = {"max_iter": 50, "tol": 1e-10}
 MAX_HISTORY_DIM = 36  # doubles per point of one history field (user_law_tile.h: kUserMaxDim)
 FACTOR_PY = float.fromhex("0x1.6a09e667f3bccp-1")  # the off-diagonal Mandel factor of the Python laws (fcamd_capi.cpp: kFactorPy)
 
@@ -85,6 +94,54 @@ def _dim_value(name, dim) -> int:
     return d
 
 
+def jacobian_directions(unknowns: int) -> tuple:
+    """directions per Jacobian pass tried for ``unknowns`` local unknowns: one pass, two passes, one unknown per pass"""
+    return tuple(sorted({unknowns, (unknowns + 1) // 2, 1}, reverse=True))
+
+
+#: implicit laws: registers per lane at each number of waves per SIMD (1: the 256 accumulation registers of a lone wave too)
+IMPLICIT_BUDGETS = {4: 128, 3: 168, 2: 256, 1: 512}
+
+
+def implicit_register_floor(unknowns: int, tangent_directions: int, state_doubles: int) -> int:
+    """registers an implicit kernel whose Jacobian is dense and varies holds at once (two per double): the Jacobian, the
+    right-hand sides of the solve (the residual, or ``tangent_directions`` columns of dr / deps), x, the strain increment and the
+    committed state.  Rungs below it are not tried: for such a law each would cost a compilation that ends in scratch (the eight
+    unknowns of VON_MISES_SWIFT_GENERAL: 27 compilations, 80 s).  A law whose Jacobian folds to constants needs less; the compiler
+    then takes less than the rung allows and ``resources["waves_per_simd"]`` shows the occupancy it reached."""
+    return 2 * (unknowns * unknowns + unknowns * max(tangent_directions, 1) + unknowns + 6 + state_doubles)
+
+
+def implicit_ladder(unknowns: int, tangent: bool, state_doubles: int = 6) -> tuple:
+    """implicit laws: the rungs tried in turn, the first without scratch is kept.  Stress-only kernel: (waves per SIMD,
+    directions per Jacobian pass), the most waves first and at each the fewest passes.  Tangent kernel: (waves, directions per
+    Jacobian pass, directions per tangent pass), the single tangent pass at any budget first as in ``AD_LADDER``; the several-pass
+    rungs evaluate the Jacobian again in every pass and take it one unknown at a time.  ``state_doubles``: committed stress and
+    history per point.  A rung whose budget is below ``implicit_register_floor`` is left out; the last rung always stays."""
+    kj = jacobian_directions(unknowns)
+    if not tangent:
+        rungs = tuple((w, k) for w in IMPLICIT_BUDGETS for k in kj)
+    else:
+        rungs = tuple((w, k, 6) for w in IMPLICIT_BUDGETS for k in kj) + tuple((w, 1, kt) for w in IMPLICIT_BUDGETS for kt in (3, 2, 1))
+    fit = tuple(r for r in rungs if IMPLICIT_BUDGETS[r[0]] >= implicit_register_floor(unknowns, r[2] if tangent else 0, state_doubles))
+    return fit or rungs[-1:]
+
+
+def _newton_options(newton) -> dict:
+    if newton is None:
+        return dict(NEWTON_DEFAULTS)
+    if not hasattr(newton, "items"):
+        raise ValueError(f"UserLaw: newton must be a dict with the keys {sorted(NEWTON_DEFAULTS)}, not {newton!r}")
+    if set(newton) != set(NEWTON_DEFAULTS):
+        raise ValueError(f"UserLaw: newton has the keys {sorted(map(str, newton))}; expected exactly {sorted(NEWTON_DEFAULTS)}")
+    max_iter, tol = newton["max_iter"], newton["tol"]
+    if isinstance(max_iter, bool) or not hasattr(max_iter, "__index__") or not 0 <= max_iter.__index__() < 2 ** 31:
+        raise ValueError(f"UserLaw: newton['max_iter'] = {max_iter!r}; expected an int >= 0")
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.floating, np.integer)) or not 0.0 < float(tol) < float("inf"):
+        raise ValueError(f"UserLaw: newton['tol'] = {tol!r}; expected a float > 0")
+    return {"max_iter": max_iter.__index__(), "tol": float(tol)}
+
+
 def refuse_user_law(law, what: str) -> None:
     """the forms of the built-in laws that user laws and objective-rate wrappers do not have (resident and multi-GPU states)"""
     if isinstance(law, jit.JitLaw):
@@ -101,13 +158,30 @@ class UserLaw(jit.JitLaw):
 
     ``tangent``: ``"explicit"`` (the source defines ``fcamd_user_point``, which writes the tangent itself) or ``"autodiff"`` (the
     source defines the function template ``fcamd_user_stress<T>``, stress and history only; the tangent comes from forward-mode
-    automatic differentiation, contract in ``csrc/jit/user_law_ad.h``)."""
+    automatic differentiation, contract in ``csrc/jit/user_law_ad.h``) or ``"implicit"`` (the source defines the templates
+    ``fcamd_user_start<T>``, ``fcamd_user_residual<T>`` and ``fcamd_user_update<T>`` over ``unknowns`` local unknowns; the kernel
+    solves the residual per point by Newton's method and forms the consistent tangent, contract in
+    ``csrc/jit/user_law_implicit.h``).
+
+    Implicit mode only: ``unknowns`` (1 to ``MAX_UNKNOWNS``, required) and ``newton`` (``{"max_iter": int >= 0, "tol": float > 0}``,
+    default 50 and 1e-10: a point is converged when every ``|r_i| <= tol``).  Both Newton values are kernel arguments, which
+    leaves such a law at most 30 parameters."""
 
     def __init__(self, source: str, parameters=None, history_dim=None, constraint: StressStrainConstraint = None,
-                 name: str = "user_law", tangent: str = "explicit", *, _rotate=None):
+                 name: str = "user_law", tangent: str = "explicit", unknowns: int = None, newton: dict = None, *, _rotate=None):
         if not isinstance(tangent, str) or tangent not in TANGENT_MODES:
             raise ValueError(f"UserLaw: tangent={tangent!r}; expected one of {TANGENT_MODES}")
         self.tangent_mode = tangent
+        implicit = tangent == "implicit"
+        if implicit:
+            if isinstance(unknowns, bool) or not hasattr(unknowns, "__index__") or not 1 <= unknowns.__index__() <= MAX_UNKNOWNS:
+                raise ValueError(f"UserLaw: unknowns={unknowns!r}; implicit laws need an int from 1 to {MAX_UNKNOWNS}")
+            self._unknowns = unknowns.__index__()
+            self._newton = _newton_options(newton)
+        else:
+            if unknowns is not None or newton is not None:
+                raise ValueError(f"UserLaw: unknowns and newton belong to tangent='implicit', not to tangent={tangent!r}")
+            self._unknowns, self._newton = None, None
         constraint = StressStrainConstraint.FULL if constraint is None else constraint
         if constraint != StressStrainConstraint.FULL:
             raise NotImplementedError(f"UserLaw: constraint {constraint.name}: user laws are FULL (3-D) only; wrap one in "
@@ -123,8 +197,9 @@ class UserLaw(jit.JitLaw):
                 if n in seen:
                     raise ValueError(f"UserLaw: name '{n}' is given more than once")
                 seen.add(n)
-        if len(params) > MAX_PARAMS:
-            raise ValueError(f"UserLaw: {len(params)} parameters; at most {MAX_PARAMS}")
+        if len(params) > (MAX_IMPLICIT_PARAMS if implicit else MAX_PARAMS):
+            raise ValueError(f"UserLaw: {len(params)} parameters; at most {MAX_IMPLICIT_PARAMS if implicit else MAX_PARAMS}"
+                             + (" for an implicit law (max_iter and tol take two slots)" if implicit else ""))
         self._param_names = tuple(n for n, _ in params)
         self._param_values = [_param_value(n, v) for n, v in params]
         self._history_dim = history_dim
@@ -133,7 +208,21 @@ class UserLaw(jit.JitLaw):
         # objective.JaumannRate: ((history field, offset), ...) of the Mandel blocks rotated with the stress before the law runs
         self._rotate = None if _rotate is None else tuple((str(f), int(o)) for f, o in _rotate)
         self._directions = None
-        if tangent == "explicit":
+        self._rung, self._rung_stress = None, None  # implicit laws: the rungs of implicit_ladder kept
+        if implicit:
+            # two code objects as in autodiff mode, each the first rung of its ladder without scratch
+            state = 6 + sum(d for _, d in self._hist)
+            for rung in implicit_ladder(self._unknowns, False, state):
+                self._compiled_stress = jit.compile_program(self._program_implicit(source, *rung, 0), self.name, KERNEL)
+                self._rung_stress = rung
+                if not self._compiled_stress.resources.get("scratch_bytes"):
+                    break
+            for rung in implicit_ladder(self._unknowns, True, state):
+                self._compiled = jit.compile_program(self._program_implicit(source, *rung), self.name, KERNEL)
+                self._rung = rung
+                if not self._compiled.resources.get("scratch_bytes"):
+                    break
+        elif tangent == "explicit":
             # cut for 4 waves per SIMD (128 VGPRs; the LDS allows no more); a law that spills there is compiled again for fewer waves
             for waves in WAVES_PER_SIMD:
                 self._compiled = jit.compile_program(self._program(source, waves), self.name, KERNEL)
@@ -160,15 +249,21 @@ class UserLaw(jit.JitLaw):
         self._args_cls = _args_type(max(1, len(self._hist)))
 
     # -- program --------------------------------------------------------------------------------------------------------
-    def _program(self, source: str, waves: int, directions: int = None) -> str:
+    def _program(self, source: str, waves: int, directions: int = None, implicit: tuple = None) -> str:
         """the generated definitions, the user's source, the kernel template.  ``directions``: autodiff mode's partials per
-        Dual (0: the stress-only kernel); None in explicit mode"""
-        ad = directions is not None
+        Dual (0: the stress-only kernel); None in explicit mode.  ``implicit``: implicit mode's (directions per Jacobian pass,
+        directions per tangent pass; 0: the stress-only kernel)"""
+        ad = directions is not None or implicit is not None
+        template = "user_law_implicit.hip" if implicit is not None else "user_law_ad.hip" if ad else "user_law.hip"
         p = self._param_names
         history, scalar = ("template <class T> struct UserHistoryT {", "T") if ad else ("struct UserHistory {", "double")
-        lines = ['#include "user_law_ad.h"' if ad else '#include "user_law_api.h"',
+        mode = [f"#define FCAMD_USER_AD_K {directions}"] if directions is not None else []
+        if implicit is not None:
+            mode = [f"#define FCAMD_USER_UNKNOWNS {self._unknowns}", f"#define FCAMD_USER_IM_KJ {implicit[0]}",
+                    f"#define FCAMD_USER_IM_KT {implicit[1]}", f"#define FCAMD_USER_IM_SLOT {len(p)}"]
+        lines = ['#include "user_law_implicit.h"' if implicit is not None else '#include "user_law_ad.h"' if ad else '#include "user_law_api.h"',
                  f"#define FCAMD_USER_WAVES {waves}",
-                 *([f"#define FCAMD_USER_AD_K {directions}"] if ad else []),
+                 *mode,
                  f"#define FCAMD_USER_NHIST {len(self._hist)}",
                  "#define FCAMD_USER_HISTORY_FIELDS(X) " + " ".join(f"X({k}, {n}, {d})" for k, (n, d) in enumerate(self._hist)),
                  "struct UserParams {" + "".join(f" double {n};" for n in p) + " };",
@@ -180,18 +275,41 @@ class UserLaw(jit.JitLaw):
         if self._rotate is not None:  # the tile prologue (user_law_tile.h) rotates the committed state with rotation.h
             lines += ["#define FCAMD_USER_ROTATE(X) " + " ".join(f"X({f}, {o})" for f, o in self._rotate), '#include "rotation.h"']
         lines.append('#line 1 "' + re.sub(r'[^A-Za-z0-9_.]', '_', self.name) + '"')
-        return "\n".join(lines) + "\n" + source + f'\n#include "{"user_law_ad.hip" if ad else "user_law.hip"}"\n'
+        return "\n".join(lines) + "\n" + source + f'\n#include "{template}"\n'
 
     def _program_ad(self, source: str, waves: int, directions: int) -> str:
         """the program of autodiff mode (``directions``: partials per Dual, 0 for the stress-only kernel)"""
         return self._program(source, waves, directions)
 
+    def _program_implicit(self, source: str, waves: int, jacobian_directions: int, tangent_directions: int) -> str:
+        """the program of implicit mode (``tangent_directions``: 0 for the stress-only kernel)"""
+        return self._program(source, waves, implicit=(jacobian_directions, tangent_directions))
+
+    @property
+    def unknowns(self):
+        """implicit laws: the number of local unknowns (None in the other modes)"""
+        return self._unknowns
+
+    @property
+    def newton(self):
+        """implicit laws: ``{"max_iter", "tol"}`` of the Newton loop (None in the other modes)"""
+        return None if self._newton is None else dict(self._newton)
+
     @property
     def resources(self) -> dict:
         """``{"vgprs", "sgprs", "scratch_bytes", "waves_per_simd", ...}`` of the compiled kernel (compiler remarks).  Autodiff
         laws: those of the tangent kernel, its ``"directions_per_pass"`` (K of Dual<K>; ceil(6 / K) passes) and under
-        ``"stress_only"`` those of the kernel of tangent=None launches."""
+        ``"stress_only"`` those of the kernel of tangent=None launches.  Implicit laws: ``"unknowns"`` and the rung kept
+        (``implicit_ladder``) -- ``"rung_waves_per_simd"`` (the budget the kernel was cut for; ``"waves_per_simd"`` is the occupancy
+        the compiler reports, which is higher where the kernel needs less), ``"jacobian_directions_per_pass"`` (K of the
+        Dual<K> that J = dr / dx is taken with; ceil(N / K) passes), ``"directions_per_pass"`` of the tangent; ``"stress_only"``
+        with its own ``"jacobian_directions_per_pass"``."""
         r = dict(self._compiled.resources)
+        if self._rung is not None:
+            r.update(unknowns=self._unknowns, rung_waves_per_simd=self._rung[0], jacobian_directions_per_pass=self._rung[1],
+                     directions_per_pass=self._rung[2])
+            r["stress_only"] = dict(self._compiled_stress.resources, rung_waves_per_simd=self._rung_stress[0],
+                                    jacobian_directions_per_pass=self._rung_stress[1])
         if self._directions is not None:
             r["directions_per_pass"] = self._directions
             r["stress_only"] = dict(self._compiled_stress.resources)
@@ -289,6 +407,9 @@ class UserLaw(jit.JitLaw):
         a.n, a.t, a.del_t, a.factor = n, float(t), float(del_t), FACTOR_PY
         for k, v in enumerate(self._param_values):
             a.params[k] = v
+        if self._newton is not None:  # FCAMD_USER_IM_SLOT: behind the law's own parameters
+            a.params[len(self._param_values)] = float(self._newton["max_iter"])
+            a.params[len(self._param_values) + 1] = self._newton["tol"]
         blocks = min(((n + 63) // 64 + 3) // 4, 512 * jit.num_cu(dev))  # a wave per 64-point tile, 4 waves per block
         jit.launch(self._compiled if tangent is not None else self._compiled_stress, dev, blocks, a, f"UserLaw '{self.name}' launch")
 

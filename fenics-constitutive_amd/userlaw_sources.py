@@ -14,6 +14,15 @@ does not ship, in autodiff form only:
 
 * ``VON_MISES_SWIFT_AD``: von Mises plasticity with Swift hardening, yield stress ``K (eps0 + alpha)^m``, radial return with a
   per-point Newton iteration on the plastic multiplier; a point that has not converged after ``max_iter`` steps returns 1.
+
+And three laws in implicit form (``tangent="implicit"``: the residual and the update from its solution; Jacobian, Newton loop,
+dense solve and consistent tangent are the kernel template's; contract in ``csrc/jit/user_law_implicit.h``):
+
+* ``VON_MISES_3D_IMPLICIT``: VonMises3D's hardening, one unknown (the plastic multiplier), the yield residual divided by the
+  yield stress.
+* ``VON_MISES_SWIFT_IMPLICIT``: the Swift law, one unknown, the residual divided by sigma_y.
+* ``VON_MISES_SWIFT_GENERAL``: the Swift law as a general return mapping in eight unknowns ``(d eps_p[6], d alpha, d gamma)``:
+  flow rule, hardening rule and yield condition as they are written down, nothing reduced by hand.
 """
 
 from __future__ import annotations
@@ -23,7 +32,8 @@ from .userlaw import UserLaw
 
 __all__ = ["LINEAR_ELASTICITY", "SPRING_MAXWELL", "VON_MISES_3D", "linear_elasticity", "spring_maxwell", "von_mises_3d",
            "LINEAR_ELASTICITY_AD", "SPRING_MAXWELL_AD", "VON_MISES_3D_AD", "VON_MISES_SWIFT_AD", "linear_elasticity_ad",
-           "spring_maxwell_ad", "von_mises_3d_ad", "von_mises_swift_ad"]
+           "spring_maxwell_ad", "von_mises_3d_ad", "von_mises_swift_ad", "VON_MISES_3D_IMPLICIT", "VON_MISES_SWIFT_IMPLICIT",
+           "VON_MISES_SWIFT_GENERAL", "von_mises_3d_implicit", "von_mises_swift_implicit", "von_mises_swift_general"]
 
 LINEAR_ELASTICITY = r"""
 // sigma += eps @ D ; tangent = D
@@ -256,6 +266,134 @@ __device__ int fcamd_user_stress(const UserParams& p, double t, double del_t, co
 }
 """
 
+# The deviatoric trial stress of the three implicit laws, its norm and the elastic predictor: the expressions of the _AD sources.
+_IMPLICIT_TRIAL = r"""
+template <class T>
+__device__ __forceinline__ void trial_state(double ka, double mu, const T (&eps)[6], const double (&sigma_n)[6], T& tr_eps,
+                                            T (&del_sigtr)[6], T (&sigtr)[6], T& sigtrn) {
+    tr_eps = (eps[0] + eps[1]) + eps[2];
+    const double tr_sig = (sigma_n[0] + sigma_n[1]) + sigma_n[2];
+    for (int i = 0; i < 6; ++i) {
+        const double I = i < 3 ? 1.0 : 0.0;
+        del_sigtr[i] = 2.0 * mu * (eps[i] - tr_eps * I / 3.0);
+        sigtr[i] = (sigma_n[i] - tr_sig * I / 3.0) + del_sigtr[i];
+    }
+    T sq = sigtr[0] * sigtr[0];
+    for (int i = 1; i < 6; ++i) sq = sq + sigtr[i] * sigtr[i];
+    sigtrn = sqrt(sq);
+}
+"""
+
+# Radial return in one unknown g, the plastic multiplier: what start, residual and update share.  YIELD(a) is the yield stress at
+# the accumulated plastic strain a.
+_RADIAL_RETURN = r"""
+// r(g) = (|s_tr| - 2 mu g - sqrt(2/3) sigma_y(alpha_n + sqrt(2/3) g)) / sigma_y; elastic (code 0, g = 0) while r(0) <= 0
+template <class T>
+__device__ int fcamd_user_start(const UserParams& p, double t, double del_t, const T (&eps)[6], const double (&sigma_n)[6],
+                                const UserHistoryT<double>& h_n, T (&x)[1]) {
+    T tr_eps, del_sigtr[6], sigtr[6], sigtrn;
+    trial_state(p.p_ka, p.p_mu, eps, sigma_n, tr_eps, del_sigtr, sigtr, sigtrn);
+    x[0] = 0.0;
+    return sigtrn - sqrt(2.0 / 3.0) * yield_stress(p, h_n.alpha[0]) > 0.0 ? 1 : 0;
+}
+
+template <class T>
+__device__ void fcamd_user_residual(const UserParams& p, double t, double del_t, const T (&eps)[6], const double (&sigma_n)[6],
+                                    const UserHistoryT<double>& h_n, const T (&x)[1], T (&r)[1]) {
+    const double s23 = sqrt(2.0 / 3.0);
+    T tr_eps, del_sigtr[6], sigtr[6], sigtrn;
+    trial_state(p.p_ka, p.p_mu, eps, sigma_n, tr_eps, del_sigtr, sigtr, sigtrn);
+    const T sy = yield_stress(p, h_n.alpha[0] + s23 * x[0]);
+    r[0] = ((sigtrn - 2.0 * p.p_mu * x[0]) - s23 * sy) / sy;
+}
+
+template <class T>
+__device__ void fcamd_user_update(const UserParams& p, double t, double del_t, const T (&eps)[6], const T (&x)[1], T (&sigma)[6],
+                                  UserHistoryT<T>& h) {
+    const double s23 = sqrt(2.0 / 3.0);
+    double sigma_n[6];
+    for (int i = 0; i < 6; ++i) sigma_n[i] = fcamd_value(sigma[i]);
+    T tr_eps, del_sigtr[6], sigtr[6], sigtrn;
+    trial_state(p.p_ka, p.p_mu, eps, sigma_n, tr_eps, del_sigtr, sigtr, sigtrn);
+    const T g = x[0];
+    for (int i = 0; i < 6; ++i) {
+        const double I = i < 3 ? 1.0 : 0.0;
+        T gn = 0.0;  // g times the flow direction; a zero trial deviator has none
+        if (sigtrn > 0.0) gn = g * (sigtr[i] / sigtrn);
+        h.eps_n[i] = h.eps_n[i] + gn;
+        sigma[i] = sigma[i] + ((p.p_ka * tr_eps * I + del_sigtr[i]) - 2.0 * p.p_mu * gn);
+    }
+    h.alpha[0] = h.alpha[0] + s23 * g;
+}
+"""
+
+VON_MISES_3D_IMPLICIT = _IMPLICIT_TRIAL + r"""
+// VonMises3D: sigma_y = y0 + (y00 - y0) (1 - exp(-w alpha))
+template <class T>
+__device__ __forceinline__ T yield_stress(const UserParams& p, const T& a) {
+    return p.p_y0 + (p.p_y00 - p.p_y0) * (1.0 - exp(-p.p_w * a));
+}
+""" + _RADIAL_RETURN
+
+VON_MISES_SWIFT_IMPLICIT = _IMPLICIT_TRIAL + r"""
+// Swift hardening: sigma_y = K (eps0 + alpha)^m
+template <class T>
+__device__ __forceinline__ T yield_stress(const UserParams& p, const T& a) {
+    return p.K * pow(p.eps0 + a, p.m);
+}
+""" + _RADIAL_RETURN
+
+VON_MISES_SWIFT_GENERAL = _IMPLICIT_TRIAL + r"""
+// von Mises plasticity with Swift hardening as a general return mapping: x = (d eps_p[6], d alpha, d gamma) and
+//   r[0..5] = d eps_p - d gamma s / |s|                       flow rule
+//   r[6]    = d alpha - sqrt(2/3) d gamma                     hardening rule
+//   r[7]    = (|s| - sqrt(2/3) sigma_y(alpha_n + d alpha)) / (2 mu)     yield condition
+// with s the deviator of sigma_n + C : (eps - d eps_p).  Nothing is reduced by hand; the 8 x 8 Jacobian is the engine's.
+template <class T>
+__device__ __forceinline__ T yield_stress(const UserParams& p, const T& a) {
+    return p.K * pow(p.eps0 + a, p.m);
+}
+
+template <class T>
+__device__ int fcamd_user_start(const UserParams& p, double t, double del_t, const T (&eps)[6], const double (&sigma_n)[6],
+                                const UserHistoryT<double>& h_n, T (&x)[8]) {
+    T tr_eps, del_sigtr[6], sigtr[6], sigtrn;
+    trial_state(p.p_ka, p.p_mu, eps, sigma_n, tr_eps, del_sigtr, sigtr, sigtrn);
+    for (int i = 0; i < 8; ++i) x[i] = 0.0;
+    return sigtrn - sqrt(2.0 / 3.0) * yield_stress(p, h_n.alpha[0]) > 0.0 ? 1 : 0;
+}
+
+template <class T>
+__device__ void fcamd_user_residual(const UserParams& p, double t, double del_t, const T (&eps)[6], const double (&sigma_n)[6],
+                                    const UserHistoryT<double>& h_n, const T (&x)[8], T (&r)[8]) {
+    const double s23 = sqrt(2.0 / 3.0);
+    T tr_eps, del_sigtr[6], sigtr[6], sigtrn;
+    trial_state(p.p_ka, p.p_mu, eps, sigma_n, tr_eps, del_sigtr, sigtr, sigtrn);
+    const T tr_p = (x[0] + x[1]) + x[2];
+    T s[6];
+    for (int i = 0; i < 6; ++i) s[i] = sigtr[i] - 2.0 * p.p_mu * (x[i] - tr_p * (i < 3 ? 1.0 : 0.0) / 3.0);
+    T sq = s[0] * s[0];
+    for (int i = 1; i < 6; ++i) sq = sq + s[i] * s[i];
+    const T sn = sqrt(sq);
+    for (int i = 0; i < 6; ++i) r[i] = x[i] - x[7] * (s[i] / sn);
+    r[6] = x[6] - s23 * x[7];
+    r[7] = (sn - s23 * yield_stress(p, h_n.alpha[0] + x[6])) / (2.0 * p.p_mu);
+}
+
+template <class T>
+__device__ void fcamd_user_update(const UserParams& p, double t, double del_t, const T (&eps)[6], const T (&x)[8], T (&sigma)[6],
+                                  UserHistoryT<T>& h) {
+    const T tr_eps = (eps[0] + eps[1]) + eps[2];
+    for (int i = 0; i < 6; ++i) {
+        const double I = i < 3 ? 1.0 : 0.0;
+        const T del_sigtr = 2.0 * p.p_mu * (eps[i] - tr_eps * I / 3.0);
+        h.eps_n[i] = h.eps_n[i] + x[i];
+        sigma[i] = sigma[i] + ((p.p_ka * tr_eps * I + del_sigtr) - 2.0 * p.p_mu * x[i]);
+    }
+    h.alpha[0] = h.alpha[0] + x[6];
+}
+"""
+
 FULL = StressStrainConstraint.FULL
 
 
@@ -299,3 +437,25 @@ def von_mises_swift_ad(parameters) -> UserLaw:
     p = {k: parameters[k] for k in ("p_ka", "p_mu", "K", "eps0", "m")}
     p["max_iter"] = float(parameters.get("max_iter", 50))
     return UserLaw(VON_MISES_SWIFT_AD, p, {"eps_n": 6, "alpha": 1}, FULL, name="von_mises_swift_ad", tangent="autodiff")
+
+
+def von_mises_3d_implicit(parameters, newton=None) -> UserLaw:
+    """``parameters``: {"p_ka", "p_mu", "p_y0", "p_y00", "p_w"}; ``newton``: {"max_iter", "tol"} (default 50, 1e-12: the residual
+    is relative to the yield stress)"""
+    return UserLaw(VON_MISES_3D_IMPLICIT, {k: parameters[k] for k in ("p_ka", "p_mu", "p_y0", "p_y00", "p_w")}, {"eps_n": 6, "alpha": 1},
+                   FULL, name="von_mises_3d_implicit", tangent="implicit", unknowns=1,
+                   newton={"max_iter": 50, "tol": 1e-12} if newton is None else newton)
+
+
+def von_mises_swift_implicit(parameters, newton=None) -> UserLaw:
+    """``parameters``: {"p_ka", "p_mu", "K", "eps0", "m"}; ``newton``: {"max_iter", "tol"} (default 50, 1e-13)"""
+    return UserLaw(VON_MISES_SWIFT_IMPLICIT, {k: parameters[k] for k in ("p_ka", "p_mu", "K", "eps0", "m")}, {"eps_n": 6, "alpha": 1},
+                   FULL, name="von_mises_swift_implicit", tangent="implicit", unknowns=1,
+                   newton={"max_iter": 50, "tol": 1e-13} if newton is None else newton)
+
+
+def von_mises_swift_general(parameters, newton=None) -> UserLaw:
+    """``parameters``: {"p_ka", "p_mu", "K", "eps0", "m"}; ``newton``: {"max_iter", "tol"} (default 50, 1e-13)"""
+    return UserLaw(VON_MISES_SWIFT_GENERAL, {k: parameters[k] for k in ("p_ka", "p_mu", "K", "eps0", "m")}, {"eps_n": 6, "alpha": 1},
+                   FULL, name="von_mises_swift_general", tangent="implicit", unknowns=8,
+                   newton={"max_iter": 50, "tol": 1e-13} if newton is None else newton)
