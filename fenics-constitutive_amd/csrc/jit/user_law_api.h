@@ -13,6 +13,11 @@
 //                                   UserHistory& h);           // in: committed history, out: trial history
 //   // return 0 = converged; any other value counts the point as not converged
 //
+// Per-point parameter fields (UserLaw(..., fields=...), user_law_fields.h): a parameter given as a field is a double member of
+// UserParams like a scalar -- the scalars first, in their order, then the fields, in theirs -- and holds the value of the lane's
+// own point; the point function does not change.  UserParams is then built per lane and tile instead of once per kernel, and in
+// the Dual passes of the other two modes a field value is a constant (zero partials), as a scalar is.
+//
 // `eps` comes from the mandel_strain call of the built-in kernels with the factor of the Python laws: it is bit-identical to
 // theirs.  The program is compiled with -ffp-contract=off, like the library: a * b + c is two roundings; write
 // __builtin_fma(a, b, c) where one rounding is meant.  Everything below lives in the global namespace of the program.

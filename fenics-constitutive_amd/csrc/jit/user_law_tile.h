@@ -6,6 +6,7 @@
 //   FCAMD_USER_HISTORY_FIELDS(X)         X(index, name, doubles per point) for every history field
 //   UserParams fcamd_user_params(const double* v)   the law's struct from the parameter values of the launch
 //   FCAMD_USER_ROTATE(X)                 only with an objective rate (objective.py: JaumannRate), rotation.h included
+//   FCAMD_USER_FIELDS(X)                 only with per-point parameter fields, user_law_fields.h included (which lists the rest)
 // and the user's source.
 //
 // Shape of the built-in evaluate kernels (fcamd_kernels.hip): 256-thread blocks, one wave per 64-point tile, a grid-stride loop
@@ -39,7 +40,21 @@ struct UserArgs {
     double t, del_t;
     double factor;               // Mandel factor of the off-diagonal strains (the Python laws')
     double params[kMaxParams];   // UserParams, in order
+#ifdef FCAMD_USER_FIELDS
+    const double* fields[kNF];   // [n] each: the per-point parameter fields, in the order of FCAMD_USER_FIELDS
+#endif
 };
+
+#ifdef FCAMD_USER_FIELDS
+// the UserParams of the lane's point in the tile starting at p0: the launch's scalars and the lane's field values
+// (user_law_fields.h).  The loads are the first of the tile; nothing waits for them before the point function.
+template <bool FULL, bool NT>
+__device__ __forceinline__ UserParams user_lane_params(const UserArgs& a, long long p0, int npts, int lane) {
+    UserFieldValues f;
+    user_fields_load<FULL, NT>(a.fields, p0, npts, lane, f);
+    return fcamd_user_params(a.params, f);
+}
+#endif
 
 // AoS tile (registers) -> per-lane values; NC <= kUserWide through one pass, else two halves of 32 points
 template <int NC>
@@ -144,12 +159,23 @@ extern "C" __global__ void __launch_bounds__(fcamd::kBlock, FCAMD_USER_WAVES) fc
     // wave index as a scalar: tile index and the tile base pointers live in SGPRs
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave);
     double* region = scratch[wave];
+#ifndef FCAMD_USER_FIELDS
     const UserParams p = fcamd_user_params(a.params);
+#endif
     const long long nfull = a.n / kWave;
     const long long wstride = (long long)gridDim.x * kWavesPerBlock;
     unsigned long long bad = 0;
     long long tile = (long long)blockIdx.x * kWavesPerBlock + wave;
+#ifdef FCAMD_USER_FIELDS  // UserParams per lane and tile
+    for (; tile < nfull; tile += wstride)
+        bad += user_tile<true, true>(a, user_lane_params<true, true>(a, tile * kWave, kWave, lane), region, tile * kWave, kWave, lane);
+    if (tile == nfull && a.n > nfull * kWave) {
+        const int npts = (int)(a.n - tile * kWave);
+        bad += user_tile<false, false>(a, user_lane_params<false, false>(a, tile * kWave, npts, lane), region, tile * kWave, npts, lane);
+    }
+#else
     for (; tile < nfull; tile += wstride) bad += user_tile<true, true>(a, p, region, tile * kWave, kWave, lane);
     if (tile == nfull && a.n > nfull * kWave) bad += user_tile<false, false>(a, p, region, tile * kWave, (int)(a.n - tile * kWave), lane);
+#endif
     if (bad != 0 && lane == 0) atomicAdd(a.nonconv, bad);
 }

@@ -83,7 +83,8 @@ def _fused_law(model, blocks):
 
     if isinstance(model, UserLaw):
         return UserLaw(model.source, model.parameters, model.history_dim, model.constraint, name=model.name,
-                       tangent=model.tangent_mode, unknowns=model.unknowns, newton=model.newton, _rotate=blocks)
+                       tangent=model.tangent_mode, unknowns=model.unknowns, newton=model.newton, fields=model.fields or None,
+                       _rotate=blocks)
     if getattr(model, "field_points", None) is not None:
         return None
     if type(model) is M.LinearElasticityModel:
@@ -201,6 +202,7 @@ class JaumannRate(jit.JitLaw):
         self._last = self.model
         hist = self._history_arrays(history)
         n = self._sizes(grad_del_u, stress, tangent, hist)
+        self._check_fields(n)
         if _is_torch(grad_del_u):
             self._check_call(grad_del_u, stress, stress, tangent, hist, hist)
             self._rotate(n, grad_del_u, stress, stress, hist, hist)
@@ -222,12 +224,18 @@ class JaumannRate(jit.JitLaw):
         self._last = self.model
         hist, hprev = self._history_arrays(history), self._history_arrays(history_prev)
         n = self._sizes(grad_del_u, stress, tangent, hist, stress_prev, hprev)
+        self._check_fields(n)
         self._check_call(grad_del_u, stress_prev, stress, tangent, hprev, hist)
         rotated = {name for name, _ in self._rot_fields}
         for (name, _), hp, h in zip(self._hist, hprev, hist):
             if name not in rotated:  # the rotation kernel writes the rotated fields; the rest is the committed state as it is
                 _check_torch(f"history['{name}']", h).copy_(_check_torch(f"history_prev['{name}']", hp))
         self._evaluate_device(t, del_t, n, grad_del_u, stress_prev, stress, tangent, hprev, hist)
+
+    def _check_fields(self, n: int) -> None:
+        """the array-level path: a user law's size check of its parameter fields, before the rotation kernel writes"""
+        if isinstance(self.model, UserLaw):
+            self.model._check_field_points(n)
 
     def _check_call(self, grad, stress_prev, stress, tangent, hist_prev, hist) -> None:
         """the array-level path on device tensors: what the wrapped law will refuse (``UserLaw._check_device_arrays``;

@@ -14,8 +14,12 @@ With ``tangent="implicit"`` the source states the law as a residual in ``unknown
 their solution (``csrc/jit/user_law_implicit.h``); the kernel template ``csrc/jit/user_law_implicit.hip`` brings the Jacobian (dual
 numbers), the per-point Newton loop, the dense solve and the consistent tangent by the implicit-function theorem.
 
-FULL constraint, scalar parameters, ``evaluate`` / ``evaluate_from``: the resident, batched, indexed and multi-GPU forms of the
-built-in laws are refused with ``NotImplementedError``.
+A parameter given in ``fields`` instead of ``parameters`` is a per-point field: one value per quadrature point, loaded by the
+point's lane (``csrc/jit/user_law_fields.h``).  The source does not change: a field is a ``double`` member of ``UserParams`` like a
+scalar.
+
+FULL constraint, ``evaluate`` / ``evaluate_from``: the resident, batched, indexed and multi-GPU forms of the built-in laws are
+refused with ``NotImplementedError``.
 """
 
 from __future__ import annotations
@@ -82,6 +86,28 @@ def _param_value(name, value) -> float:
         raise NotImplementedError(f"UserLaw: parameter '{name}' is an array; user laws take scalar parameters only "
                                   "(per-point parameter fields are not supported)")
     return float(value)
+
+
+def _field_value(name, value) -> np.ndarray:
+    """a host copy of the per-point field ``value``: a 1-D float64 NumPy array or ROCm tensor over ``len(value)`` >= 1 points
+    (one element: a field over one point).  The messages of ``device.parameter_field``."""
+    if _is_torch(value):
+        import torch
+
+        shape, is_f64 = tuple(value.shape), value.dtype == torch.float64
+    elif isinstance(value, np.ndarray):
+        shape, is_f64 = value.shape, value.dtype == np.float64
+    else:
+        raise TypeError(f"UserLaw: field '{name}' must be a 1-D float64 NumPy array or ROCm tensor, got {type(value).__name__}")
+    if len(shape) != 1:
+        raise ValueError(f"parameter field '{name}' must be 1-D, got shape {shape}")
+    if not is_f64:
+        raise TypeError(f"parameter field '{name}' must be float64, got {value.dtype}")
+    if shape[0] < 1:
+        raise ValueError(f"parameter field '{name}' is empty; a field has one value per point")
+    if _is_torch(value):
+        return value.detach().cpu().numpy().copy()
+    return np.array(value, dtype=np.float64, copy=True)
 
 
 def _dim_value(name, dim) -> int:
@@ -156,6 +182,12 @@ class UserLaw(jit.JitLaw):
     one code object.  ``history_dim``: name -> doubles per point (an int or a tuple, whose product counts), or None.  The
     names are C identifiers, not C++ keywords, and do not repeat.  FULL constraint only.
 
+    ``fields``: name -> 1-D float64 NumPy array or ROCm tensor, a parameter with one value per point (a dict or a list of pairs;
+    an array in ``parameters`` stays refused).  All fields have the same length, ``field_points``, and every call must have that
+    many points.  The values are copied here and uploaded once per device on first use.  A field is a ``double`` member of
+    ``UserParams`` behind the scalars, so a source reads ``p.K`` whether ``K`` is a scalar or a field; parameters and fields
+    together count against the 32.  Laws that differ only in field values or lengths share one code object.
+
     ``tangent``: ``"explicit"`` (the source defines ``fcamd_user_point``, which writes the tangent itself) or ``"autodiff"`` (the
     source defines the function template ``fcamd_user_stress<T>``, stress and history only; the tangent comes from forward-mode
     automatic differentiation, contract in ``csrc/jit/user_law_ad.h``) or ``"implicit"`` (the source defines the templates
@@ -168,7 +200,7 @@ class UserLaw(jit.JitLaw):
     leaves such a law at most 30 parameters."""
 
     def __init__(self, source: str, parameters=None, history_dim=None, constraint: StressStrainConstraint = None,
-                 name: str = "user_law", tangent: str = "explicit", unknowns: int = None, newton: dict = None, *, _rotate=None):
+                 name: str = "user_law", tangent: str = "explicit", unknowns: int = None, newton: dict = None, fields=None, *, _rotate=None):
         if not isinstance(tangent, str) or tangent not in TANGENT_MODES:
             raise ValueError(f"UserLaw: tangent={tangent!r}; expected one of {TANGENT_MODES}")
         self.tangent_mode = tangent
@@ -190,18 +222,26 @@ class UserLaw(jit.JitLaw):
         self.name = str(name)
         params = _items(parameters)
         hist = _items(history_dim)
+        flds = _items(fields)
         seen = set()
-        for what, pairs in (("parameter", params), ("history", hist)):
+        for what, pairs in (("parameter", params), ("field", flds), ("history", hist)):
             for n, _ in pairs:
                 _check_name(n, what)
                 if n in seen:
                     raise ValueError(f"UserLaw: name '{n}' is given more than once")
                 seen.add(n)
-        if len(params) > (MAX_IMPLICIT_PARAMS if implicit else MAX_PARAMS):
-            raise ValueError(f"UserLaw: {len(params)} parameters; at most {MAX_IMPLICIT_PARAMS if implicit else MAX_PARAMS}"
+        if len(params) + len(flds) > (MAX_IMPLICIT_PARAMS if implicit else MAX_PARAMS):
+            raise ValueError(f"UserLaw: {len(params) + len(flds)} parameters" + (" and fields" if flds else "")
+                             + f"; at most {MAX_IMPLICIT_PARAMS if implicit else MAX_PARAMS}"
                              + (" for an implicit law (max_iter and tol take two slots)" if implicit else ""))
         self._param_names = tuple(n for n, _ in params)
         self._param_values = [_param_value(n, v) for n, v in params]
+        # per-point parameter fields: host copies, uploaded once per device on first use (_field_ptrs)
+        self._field_names = tuple(n for n, _ in flds)
+        self._field_values = [_field_value(n, v) for n, v in flds]
+        if len({len(f) for f in self._field_values}) > 1:
+            raise ValueError(f"all parameter fields of a law have the same length, got {sorted({len(f) for f in self._field_values})}")
+        self._field_dev = {}  # device -> the fields' device copies
         self._history_dim = history_dim
         self._hist = [(n, _dim_value(n, d)) for n, d in hist]
         self.source = source
@@ -246,7 +286,7 @@ class UserLaw(jit.JitLaw):
                               f"(VGPRs: {c.resources.get('vgprs')}); register spills cost memory bandwidth", UserWarning, stacklevel=2)
         self._counters = {}  # device -> int64 device word (non-converged points of the last launch)
         self._empty = {}  # device -> the last call had no points
-        self._args_cls = _args_type(max(1, len(self._hist)))
+        self._args_cls = _args_type(max(1, len(self._hist)), len(self._field_names))
 
     # -- program --------------------------------------------------------------------------------------------------------
     def _program(self, source: str, waves: int, directions: int = None, implicit: tuple = None) -> str:
@@ -255,7 +295,7 @@ class UserLaw(jit.JitLaw):
         directions per tangent pass; 0: the stress-only kernel)"""
         ad = directions is not None or implicit is not None
         template = "user_law_implicit.hip" if implicit is not None else "user_law_ad.hip" if ad else "user_law.hip"
-        p = self._param_names
+        p, f = self._param_names, self._field_names
         history, scalar = ("template <class T> struct UserHistoryT {", "T") if ad else ("struct UserHistory {", "double")
         mode = [f"#define FCAMD_USER_AD_K {directions}"] if directions is not None else []
         if implicit is not None:
@@ -266,12 +306,20 @@ class UserLaw(jit.JitLaw):
                  *mode,
                  f"#define FCAMD_USER_NHIST {len(self._hist)}",
                  "#define FCAMD_USER_HISTORY_FIELDS(X) " + " ".join(f"X({k}, {n}, {d})" for k, (n, d) in enumerate(self._hist)),
-                 "struct UserParams {" + "".join(f" double {n};" for n in p) + " };",
-                 history + "".join(f" {scalar} {n}[{d}];" for n, d in self._hist) + " };",
-                 "__device__ __forceinline__ UserParams fcamd_user_params(const double* v) {",
-                 "    UserParams p;" + "".join(f" p.{n} = v[{k}];" for k, n in enumerate(p)),
-                 "    return p;",
-                 "}"]
+                 "struct UserParams {" + "".join(f" double {n};" for n in p + f) + " };",
+                 history + "".join(f" {scalar} {n}[{d}];" for n, d in self._hist) + " };"]
+        if f:  # per lane: the launch's scalars, then the lane's field values (user_law_fields.h)
+            lines += [f"#define FCAMD_USER_NFIELDS {len(f)}",
+                      "#define FCAMD_USER_FIELDS(X) " + " ".join(f"X({k}, {n})" for k, n in enumerate(f)),
+                      '#include "user_law_fields.h"',
+                      "__device__ __forceinline__ UserParams fcamd_user_params(const double* v, const fcamd_user::UserFieldValues& f) {",
+                      "    UserParams p;" + "".join(f" p.{n} = v[{k}];" for k, n in enumerate(p))
+                      + "".join(f" p.{n} = f.v[{k}];" for k, n in enumerate(f))]
+        else:
+            lines += ["__device__ __forceinline__ UserParams fcamd_user_params(const double* v) {",
+                      "    UserParams p;" + "".join(f" p.{n} = v[{k}];" for k, n in enumerate(p))]
+        lines += ["    return p;",
+                  "}"]
         if self._rotate is not None:  # the tile prologue (user_law_tile.h) rotates the committed state with rotation.h
             lines += ["#define FCAMD_USER_ROTATE(X) " + " ".join(f"X({f}, {o})" for f, o in self._rotate), '#include "rotation.h"']
         lines.append('#line 1 "' + re.sub(r'[^A-Za-z0-9_.]', '_', self.name) + '"')
@@ -330,7 +378,40 @@ class UserLaw(jit.JitLaw):
 
     @property
     def parameters(self) -> dict:
+        """the scalar parameters (the fields: ``fields``)"""
         return dict(zip(self._param_names, self._param_values))
+
+    # -- per-point parameter fields -----------------------------------------------------------------------------------------
+    @property
+    def field_points(self):
+        """number of points of the law's parameter fields (``None``: no fields, every parameter is a scalar)"""
+        return len(self._field_values[0]) if self._field_values else None
+
+    @property
+    def field_names(self) -> tuple:
+        """the parameters given per point, in the order of ``UserParams``"""
+        return self._field_names
+
+    @property
+    def fields(self) -> dict:
+        """name -> a copy of the field's values"""
+        return {n: f.copy() for n, f in zip(self._field_names, self._field_values)}
+
+    def _check_field_points(self, n: int) -> None:
+        """a call over ``n`` points fits the fields (``DeviceLaw._field_ptrs``' check), before anything is launched or written"""
+        if self._field_values and n != self.field_points:
+            raise AssertionError(f"{type(self).__name__}: the parameter fields have {self.field_points} points, the call has {n}")
+
+    def _field_ptrs(self, device: int) -> list:
+        """the device addresses of the fields on ``device``, uploaded there once"""
+        dev = self._field_dev.get(device)
+        if dev is None:
+            import torch
+
+            from .hostio import to_device
+
+            dev = self._field_dev[device] = [to_device(f, torch.device("cuda", device)) for f in self._field_values]
+        return [f.data_ptr() for f in dev]
 
     def update(self) -> None:
         pass
@@ -349,6 +430,7 @@ class UserLaw(jit.JitLaw):
         self._refuse_batched()
         hist = self._history_arrays(history)
         n = self._sizes(grad_del_u, stress, tangent, hist)
+        self._check_field_points(n)
         if _is_torch(grad_del_u):
             self._evaluate_device(t, del_t, n, grad_del_u, stress, stress, tangent, hist, hist)
             if check:
@@ -362,6 +444,7 @@ class UserLaw(jit.JitLaw):
         self._refuse_batched()
         hist, hprev = self._history_arrays(history), self._history_arrays(history_prev)
         n = self._sizes(grad_del_u, stress, tangent, hist, stress_prev, hprev)
+        self._check_field_points(n)
         if not _is_torch(grad_del_u):
             raise TypeError("UserLaw.evaluate_from takes device tensors (use evaluate for NumPy arrays)")
         self._evaluate_device(t, del_t, n, grad_del_u, stress_prev, stress, tangent, hprev, hist)
@@ -393,6 +476,7 @@ class UserLaw(jit.JitLaw):
 
     def _evaluate_device(self, t, del_t, n, grad, stress_prev, stress, tangent, hist_prev, hist) -> None:
         dev = self._check_device_arrays(grad, stress_prev, stress, tangent, hist_prev, hist)
+        self._check_field_points(n)  # the kernel reads n values of every field
         self._empty[dev] = n == 0
         if n == 0:  # nothing is launched (device_stats: 0)
             return
@@ -410,6 +494,8 @@ class UserLaw(jit.JitLaw):
         if self._newton is not None:  # FCAMD_USER_IM_SLOT: behind the law's own parameters
             a.params[len(self._param_values)] = float(self._newton["max_iter"])
             a.params[len(self._param_values) + 1] = self._newton["tol"]
+        for k, ptr in enumerate(self._field_ptrs(dev) if self._field_values else ()):
+            a.fields[k] = ptr
         blocks = min(((n + 63) // 64 + 3) // 4, 512 * jit.num_cu(dev))  # a wave per 64-point tile, 4 waves per block
         jit.launch(self._compiled if tangent is not None else self._compiled_stress, dev, blocks, a, f"UserLaw '{self.name}' launch")
 
@@ -423,13 +509,13 @@ class UserLaw(jit.JitLaw):
         return int(to_host(c)[0])
 
 
-def _args_type(nh: int):
-    """ctypes mirror of UserArgs (user_law_tile.h) for ``nh`` history slots"""
+def _args_type(nh: int, nf: int = 0):
+    """ctypes mirror of UserArgs (user_law_tile.h) for ``nh`` history slots and ``nf`` parameter fields (behind the other members)"""
     vp = C.c_void_p
 
     class UserArgs(C.Structure):
         _fields_ = [("grad", vp), ("stress_in", vp), ("stress_out", vp), ("tangent", vp), ("h_in", vp * nh), ("h_out", vp * nh),
                     ("nonconv", vp), ("n", C.c_int64), ("t", C.c_double), ("del_t", C.c_double), ("factor", C.c_double),
-                    ("params", C.c_double * MAX_PARAMS)]
+                    ("params", C.c_double * MAX_PARAMS)] + ([("fields", vp * nf)] if nf else [])
 
     return UserArgs

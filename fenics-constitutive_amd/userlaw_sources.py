@@ -23,6 +23,9 @@ dense solve and consistent tangent are the kernel template's; contract in ``csrc
 * ``VON_MISES_SWIFT_IMPLICIT``: the Swift law, one unknown, the residual divided by sigma_y.
 * ``VON_MISES_SWIFT_GENERAL``: the Swift law as a general return mapping in eight unknowns ``(d eps_p[6], d alpha, d gamma)``:
   flow rule, hardening rule and yield condition as they are written down, nothing reduced by hand.
+
+Every helper constructor takes a NumPy array or a tensor for any of its parameters and hands it to ``UserLaw(fields=...)``: a
+per-point parameter field.  Scalars go where they always went, and a call with scalars only builds the program it always built.
 """
 
 from __future__ import annotations
@@ -395,67 +398,82 @@ __device__ void fcamd_user_update(const UserParams& p, double t, double del_t, c
 """
 
 FULL = StressStrainConstraint.FULL
+_VM = ("p_ka", "p_mu", "p_y0", "p_y00", "p_w")
+_SWIFT = ("p_ka", "p_mu", "K", "eps0", "m")
+
+
+def _split(parameters, names) -> dict:
+    """``{"parameters": ..., "fields": ...}`` of UserLaw for the law's parameter ``names``: a value that is a NumPy array or a tensor
+    is a per-point field, the rest are the scalars they always were"""
+    from .device import _is_torch
+
+    import numpy as np
+
+    is_field = {k: isinstance(parameters[k], np.ndarray) or _is_torch(parameters[k]) for k in names}
+    return {"parameters": {k: parameters[k] for k in names if not is_field[k]},
+            "fields": {k: parameters[k] for k in names if is_field[k]} or None}
 
 
 def linear_elasticity(parameters) -> UserLaw:
     """``parameters``: {"E", "nu"}"""
-    return UserLaw(LINEAR_ELASTICITY, {"E": parameters["E"], "nu": parameters["nu"]}, None, FULL, name="linear_elasticity")
+    return UserLaw(LINEAR_ELASTICITY, history_dim=None, constraint=FULL, name="linear_elasticity", **_split(parameters, ("E", "nu")))
 
 
 def spring_maxwell(parameters) -> UserLaw:
     """``parameters``: {"E0", "E1", "tau", "nu"}"""
-    return UserLaw(SPRING_MAXWELL, {k: parameters[k] for k in ("E0", "E1", "tau", "nu")}, {"strain_visco": 6, "strain": 6}, FULL,
-                   name="spring_maxwell")
+    return UserLaw(SPRING_MAXWELL, history_dim={"strain_visco": 6, "strain": 6}, constraint=FULL, name="spring_maxwell",
+                   **_split(parameters, ("E0", "E1", "tau", "nu")))
 
 
 def von_mises_3d(parameters) -> UserLaw:
     """``parameters``: {"p_ka", "p_mu", "p_y0", "p_y00", "p_w"}"""
-    return UserLaw(VON_MISES_3D, {k: parameters[k] for k in ("p_ka", "p_mu", "p_y0", "p_y00", "p_w")}, {"eps_n": 6, "alpha": 1}, FULL,
-                   name="von_mises_3d")
+    return UserLaw(VON_MISES_3D, history_dim={"eps_n": 6, "alpha": 1}, constraint=FULL, name="von_mises_3d",
+                   **_split(parameters, _VM))
 
 
 def linear_elasticity_ad(parameters) -> UserLaw:
     """``parameters``: {"E", "nu"}"""
-    return UserLaw(LINEAR_ELASTICITY_AD, {"E": parameters["E"], "nu": parameters["nu"]}, None, FULL, name="linear_elasticity_ad",
-                   tangent="autodiff")
+    return UserLaw(LINEAR_ELASTICITY_AD, history_dim=None, constraint=FULL, name="linear_elasticity_ad", tangent="autodiff",
+                   **_split(parameters, ("E", "nu")))
 
 
 def spring_maxwell_ad(parameters) -> UserLaw:
     """``parameters``: {"E0", "E1", "tau", "nu"}"""
-    return UserLaw(SPRING_MAXWELL_AD, {k: parameters[k] for k in ("E0", "E1", "tau", "nu")}, {"strain_visco": 6, "strain": 6}, FULL,
-                   name="spring_maxwell_ad", tangent="autodiff")
+    return UserLaw(SPRING_MAXWELL_AD, history_dim={"strain_visco": 6, "strain": 6}, constraint=FULL, name="spring_maxwell_ad",
+                   tangent="autodiff", **_split(parameters, ("E0", "E1", "tau", "nu")))
 
 
 def von_mises_3d_ad(parameters) -> UserLaw:
     """``parameters``: {"p_ka", "p_mu", "p_y0", "p_y00", "p_w"}"""
-    return UserLaw(VON_MISES_3D_AD, {k: parameters[k] for k in ("p_ka", "p_mu", "p_y0", "p_y00", "p_w")}, {"eps_n": 6, "alpha": 1},
-                   FULL, name="von_mises_3d_ad", tangent="autodiff")
+    return UserLaw(VON_MISES_3D_AD, history_dim={"eps_n": 6, "alpha": 1}, constraint=FULL, name="von_mises_3d_ad",
+                   tangent="autodiff", **_split(parameters, _VM))
 
 
 def von_mises_swift_ad(parameters) -> UserLaw:
     """``parameters``: {"p_ka", "p_mu", "K", "eps0", "m"} and optionally "max_iter" (Newton steps; default 50)"""
-    p = {k: parameters[k] for k in ("p_ka", "p_mu", "K", "eps0", "m")}
-    p["max_iter"] = float(parameters.get("max_iter", 50))
-    return UserLaw(VON_MISES_SWIFT_AD, p, {"eps_n": 6, "alpha": 1}, FULL, name="von_mises_swift_ad", tangent="autodiff")
+    p = _split(parameters, _SWIFT)
+    p["parameters"]["max_iter"] = float(parameters.get("max_iter", 50))  # a step count: uniform
+    return UserLaw(VON_MISES_SWIFT_AD, history_dim={"eps_n": 6, "alpha": 1}, constraint=FULL, name="von_mises_swift_ad",
+                   tangent="autodiff", **p)
 
 
 def von_mises_3d_implicit(parameters, newton=None) -> UserLaw:
     """``parameters``: {"p_ka", "p_mu", "p_y0", "p_y00", "p_w"}; ``newton``: {"max_iter", "tol"} (default 50, 1e-12: the residual
     is relative to the yield stress)"""
-    return UserLaw(VON_MISES_3D_IMPLICIT, {k: parameters[k] for k in ("p_ka", "p_mu", "p_y0", "p_y00", "p_w")}, {"eps_n": 6, "alpha": 1},
-                   FULL, name="von_mises_3d_implicit", tangent="implicit", unknowns=1,
-                   newton={"max_iter": 50, "tol": 1e-12} if newton is None else newton)
+    return UserLaw(VON_MISES_3D_IMPLICIT, history_dim={"eps_n": 6, "alpha": 1}, constraint=FULL, name="von_mises_3d_implicit",
+                   tangent="implicit", unknowns=1, newton={"max_iter": 50, "tol": 1e-12} if newton is None else newton,
+                   **_split(parameters, _VM))
 
 
 def von_mises_swift_implicit(parameters, newton=None) -> UserLaw:
     """``parameters``: {"p_ka", "p_mu", "K", "eps0", "m"}; ``newton``: {"max_iter", "tol"} (default 50, 1e-13)"""
-    return UserLaw(VON_MISES_SWIFT_IMPLICIT, {k: parameters[k] for k in ("p_ka", "p_mu", "K", "eps0", "m")}, {"eps_n": 6, "alpha": 1},
-                   FULL, name="von_mises_swift_implicit", tangent="implicit", unknowns=1,
-                   newton={"max_iter": 50, "tol": 1e-13} if newton is None else newton)
+    return UserLaw(VON_MISES_SWIFT_IMPLICIT, history_dim={"eps_n": 6, "alpha": 1}, constraint=FULL, name="von_mises_swift_implicit",
+                   tangent="implicit", unknowns=1, newton={"max_iter": 50, "tol": 1e-13} if newton is None else newton,
+                   **_split(parameters, _SWIFT))
 
 
 def von_mises_swift_general(parameters, newton=None) -> UserLaw:
     """``parameters``: {"p_ka", "p_mu", "K", "eps0", "m"}; ``newton``: {"max_iter", "tol"} (default 50, 1e-13)"""
-    return UserLaw(VON_MISES_SWIFT_GENERAL, {k: parameters[k] for k in ("p_ka", "p_mu", "K", "eps0", "m")}, {"eps_n": 6, "alpha": 1},
-                   FULL, name="von_mises_swift_general", tangent="implicit", unknowns=8,
-                   newton={"max_iter": 50, "tol": 1e-13} if newton is None else newton)
+    return UserLaw(VON_MISES_SWIFT_GENERAL, history_dim={"eps_n": 6, "alpha": 1}, constraint=FULL, name="von_mises_swift_general",
+                   tangent="implicit", unknowns=8, newton={"max_iter": 50, "tol": 1e-13} if newton is None else newton,
+                   **_split(parameters, _SWIFT))
