@@ -328,6 +328,8 @@ int timing_end(fcamd_model* m) {
 }  // namespace
 
 namespace fcamd {
+static bool is_split(const fcamd_model* m, int flags) { return (flags & FCAMD_EVAL_SPLIT_HISTORY) != 0 && has_split_history(m->law); }
+
 int validate_call(const fcamd_model* m, double del_t, int64_t n, const void* grad,
                   const void* stress_prev, const void* stress, const void* const* hist_prev,
                   const void* const* hist, int n_hist, int flags) {
@@ -354,6 +356,38 @@ int validate_call(const fcamd_model* m, double del_t, int64_t n, const void* gra
         return fail(FCAMD_ERR_DEL_T, "Time step must be defined and positive.");
     if (n > 0 && (!grad || !stress || !stress_prev))
         return fail(FCAMD_ERR_BAD_ARG, "grad_del_u / stress pointer is NULL");
+    return FCAMD_OK;
+}
+
+// (both entries have run validate_call: the history tables of a law with history are there)
+int check_protocol(const fcamd_model* m, int64_t n, const fcamd_eval_args* x) {
+    if (x->flags & ~(FCAMD_EVAL_SPARSE_TANGENT | FCAMD_EVAL_SPLIT_HISTORY | FCAMD_EVAL_PACKED_HISTORY | FCAMD_EVAL_PARAM_FIELDS))
+        return fail(FCAMD_ERR_UNSUPPORTED, "unknown FCAMD_EVAL_* flag in 0x%x (2, FCAMD_EVAL_DELTA_HISTORY of ABI 0.3, was removed in 0.4)", x->flags);
+    if (x->history_mask && !has_sparse_history(m->law))
+        return fail(FCAMD_ERR_UNSUPPORTED, "sparse trial history exists for the plasticity laws only");
+    if ((x->flags & FCAMD_EVAL_PACKED_HISTORY) && n > 0) {
+        const bool split = is_split(m, x->flags);
+        if (m->law != FCAMD_VON_MISES_3D && !split)
+            return fail(FCAMD_ERR_UNSUPPORTED, "FCAMD_EVAL_PACKED_HISTORY exists for VonMises3D and, with FCAMD_EVAL_SPLIT_HISTORY, for the "
+                                               "comfe-rs plasticity laws");
+        if (!x->history_mask || !x->packed_mask_prev || !x->packed_mask)
+            return fail(FCAMD_ERR_BAD_ARG, "FCAMD_EVAL_PACKED_HISTORY needs history_mask, packed_mask_prev and packed_mask");
+        if (x->parent_rows && m->law != FCAMD_VON_MISES_3D)
+            return fail(FCAMD_ERR_UNSUPPORTED, "FCAMD_EVAL_PACKED_HISTORY with parent_rows: VonMises3D only");
+        const int kd = split ? 1 : 0;
+        if (x->history[kd] == x->history_prev[kd] || x->packed_mask == x->packed_mask_prev)
+            return fail(FCAMD_ERR_BAD_ARG, "FCAMD_EVAL_PACKED_HISTORY needs trial plastic-strain and mask arrays of their own");
+    }
+    if (!aligned16(x->stress) || !aligned16(x->stress_prev))
+        return fail(FCAMD_ERR_ALIGN, "device arrays must be 16-byte aligned");
+    for (int k = 0; k < x->n_hist; ++k)
+        if (!aligned16(x->history[k]) || !aligned16(x->history_prev[k]))
+            return fail(FCAMD_ERR_ALIGN, "device history arrays must be 16-byte aligned");
+    if (x->flags & FCAMD_EVAL_SPLIT_HISTORY) {
+        if (m->constraint != FCAMD_FULL) return fail(FCAMD_ERR_UNSUPPORTED, "FCAMD_EVAL_SPLIT_HISTORY: 3-D laws only");
+        if ((x->history[0] == x->history_prev[0]) != (x->history[1] == x->history_prev[1]))
+            return fail(FCAMD_ERR_BAD_ARG, "FCAMD_EVAL_SPLIT_HISTORY: both history arrays in place or both out of place");
+    }
     return FCAMD_OK;
 }
 }  // namespace fcamd
@@ -385,6 +419,51 @@ int grid_for(fcamd_model* m, int64_t n) {
 namespace fcamd {
 constexpr int kFlagExactTangentRows = 16;  // kernels/tangent_writers.h (library-internal bit of EvalArgs::flags)
 
+Launch launch_of(const fcamd_model* m, const fcamd_eval_args* x) {
+    Launch l;
+    l.grad = x->grad_del_u;
+    l.stress_prev = x->stress_prev;
+    l.stress = x->stress;
+    l.stress2 = x->stress2;
+    l.tangent = x->tangent;
+    for (int k = 0; k < x->n_hist && k < FCAMD_MAX_HISTORY; ++k) {
+        l.hist_prev[k] = x->history_prev[k];
+        l.hist[k] = x->history[k];
+    }
+    l.rows = x->parent_rows;
+    l.hmask = reinterpret_cast<unsigned long long*>(x->history_mask);
+    if (x->flags & FCAMD_EVAL_PACKED_HISTORY) {
+        l.emask_prev = reinterpret_cast<const unsigned long long*>(x->packed_mask_prev);
+        l.emask = reinterpret_cast<unsigned long long*>(x->packed_mask);
+    }
+    l.counters = reinterpret_cast<unsigned long long*>(x->counters);
+    l.fields = has_fields(m, fields_of(x)) ? fields_of(x) : nullptr;
+    l.flags = x->flags;
+    return l;
+}
+
+Launch slice(const fcamd_model* m, const Launch& l, int64_t p0) {
+    Launch s = l;
+    const bool split = is_split(m, l.flags);
+    auto advance = [p0](auto*& p, int64_t per_point) { if (p) p += per_point * p0; };
+    advance(s.grad, m->dims.gd2);
+    advance(s.stress_prev, m->dims.sd);
+    advance(s.stress, m->dims.sd);
+    advance(s.stress2, m->dims.sd);
+    advance(s.tangent, m->dims.sd * m->dims.sd);
+    for (int k = 0; k < (split ? 2 : m->info.n_hist); ++k) {
+        const int d = split ? (k == 0 ? 1 : 6) : m->info.hist[k].dim;  // split: [scalar (n), eps_p rows (6 n)]
+        advance(s.hist_prev[k], d);
+        advance(s.hist[k], d);
+    }
+    advance(s.rows, 1);
+    s.hmask = l.hmask ? l.hmask + p0 / 64 : nullptr;
+    s.emask_prev = l.emask_prev ? l.emask_prev + p0 / 64 : nullptr;
+    s.emask = l.emask ? l.emask + p0 / 64 : nullptr;
+    s.field_p0 += p0;
+    return s;
+}
+
 // does the device address `p` lie in host memory this context has mapped (registered caller ranges, the page-locked scratch)?
 static bool host_mapped(fcamd_context* c, const void* p) {
     const char* q = static_cast<const char*>(p);
@@ -396,43 +475,40 @@ static bool host_mapped(fcamd_context* c, const void* p) {
 }
 
 // the kernel arguments of one launch (device pointers already validated)
-static void fill_args(fcamd_model* m, double del_t, int64_t n, const double* grad, const double* stress_prev,
-                      double* stress, double* tangent, const double* const* hprev, double* const* hcur, const int* rows,
-                      unsigned long long* hmask, int flags, double* stress2,
-                      unsigned long long* counters, const unsigned long long* emask_prev, unsigned long long* emask, EvalArgs& a) {
-    a.grad = grad;
-    a.stress_in = stress_prev;
-    a.stress_out = stress;
-    a.stress_out2 = stress2;
-    a.tangent = tangent;
-    const bool split = (flags & FCAMD_EVAL_SPLIT_HISTORY) != 0 && has_split_history(m->law);
+static void fill_args(fcamd_model* m, double del_t, int64_t n, const Launch& l, EvalArgs& a) {
+    a.grad = l.grad;
+    a.stress_in = l.stress_prev;
+    a.stress_out = l.stress;
+    a.stress_out2 = l.stress2;
+    a.tangent = l.tangent;
+    const bool split = is_split(m, l.flags);
     const int nh = split ? 2 : m->info.n_hist;
-    a.h0_in = nh > 0 ? hprev[0] : nullptr;
-    a.h0_out = nh > 0 ? hcur[0] : nullptr;
-    a.h1_in = nh > 1 ? hprev[1] : nullptr;
-    a.h1_out = nh > 1 ? hcur[1] : nullptr;
-    a.rows = rows;
+    a.h0_in = nh > 0 ? l.hist_prev[0] : nullptr;
+    a.h0_out = nh > 0 ? l.hist[0] : nullptr;
+    a.h1_in = nh > 1 ? l.hist_prev[1] : nullptr;
+    a.h1_out = nh > 1 ? l.hist[1] : nullptr;
+    a.rows = l.rows;
     a.cache3d = nullptr;
-    a.hmask = hmask;
+    a.hmask = l.hmask;
     a.flags = split ? FCAMD_EVAL_SPLIT_HISTORY : 0;
-    if (hmask) {
-        if (tangent) a.flags |= flags & FCAMD_EVAL_SPARSE_TANGENT;  // needs an array that holds the previous tangent
+    if (l.hmask) {
+        if (l.tangent) a.flags |= l.flags & FCAMD_EVAL_SPARSE_TANGENT;  // needs an array that holds the previous tangent
         // the tangent is page-locked host memory written over PCIe (a registered range or the bounce scratch): bare rows, no granules
-        if ((a.flags & FCAMD_EVAL_SPARSE_TANGENT) && host_mapped(m->ctx, tangent)) a.flags |= kFlagExactTangentRows;
+        if ((a.flags & FCAMD_EVAL_SPARSE_TANGENT) && host_mapped(m->ctx, l.tangent)) a.flags |= kFlagExactTangentRows;
         // (with parent_rows: VonMises3D only -- the indexed split-history kernels would need instantiations of their own)
-        if ((m->law == FCAMD_VON_MISES_3D || (split && !rows)) && emask_prev && emask) a.flags |= flags & FCAMD_EVAL_PACKED_HISTORY;
+        if ((m->law == FCAMD_VON_MISES_3D || (split && !l.rows)) && l.emask_prev && l.emask) a.flags |= l.flags & FCAMD_EVAL_PACKED_HISTORY;
     }
     // (measurement device, context option "twin_masks":) the synthetic twin of the packed sparse-protocol VonMises3D launch
-    if (m->ctx->twin_masks && m->law == FCAMD_VON_MISES_3D && !rows && (a.flags & FCAMD_EVAL_PACKED_HISTORY)) {
+    if (m->ctx->twin_masks && m->law == FCAMD_VON_MISES_3D && !l.rows && (a.flags & FCAMD_EVAL_PACKED_HISTORY)) {
         a.flags |= 64;  // kernels/tangent_writers.h: kFlagTwin
         a.cache3d = reinterpret_cast<double*>(m->ctx->twin_masks);
     }
     // (library-internal, host entries only:) `tangent` is the ring of 8 doubles per point, the host rebuilds the rows
-    if (tangent && (flags & kFlagTangentParamsHost)) a.flags = (a.flags & ~FCAMD_EVAL_SPARSE_TANGENT) | kFlagTangentParamsHost;
-    a.emask_in = emask_prev;
-    a.emask_out = emask;
+    if (l.tangent && (l.flags & kFlagTangentParamsHost)) a.flags = (a.flags & ~FCAMD_EVAL_SPARSE_TANGENT) | kFlagTangentParamsHost;
+    a.emask_in = l.emask_prev;
+    a.emask_out = l.emask;
     a.n = n;
-    a.counters = counters ? counters : m->d_counters;  // caller-owned counters are always reset by the launch
+    a.counters = l.counters ? l.counters : m->d_counters;  // caller-owned counters are always reset by the launch
     const Options& o = m->ctx->opt;
     a.masked_max = o.masked_max >= 0 ? o.masked_max  // split history: 48-byte eps_p rows, as VonMises3D's eps_n
                                      : ((m->law == FCAMD_VON_MISES_3D || split) ? kMaskedRowMaxVonMises : kMaskedRowMaxRows7);
@@ -479,22 +555,17 @@ static void field_tables(const fcamd_model* m, EvalArgs& a) {
         for (int j = 0; j < 6; ++j) a.tb.a[6 * i + j] = (i < 3 && j < 3) ? 1.0 : 0.0;
 }
 
-int enqueue(fcamd_model* m, double del_t, int64_t n, const double* grad, const double* stress_prev,
-            double* stress, double* tangent, const double* const* hprev, double* const* hcur,
-            hipStream_t stream, bool reset_counters, const int* rows,
-            unsigned long long* hmask, int flags, double* stress2,
-            unsigned long long* counters, const unsigned long long* emask_prev, unsigned long long* emask,
-            const double* const* fields, int64_t field_p0) {
+int enqueue(fcamd_model* m, double del_t, int64_t n, const Launch& l, hipStream_t stream, bool reset_counters) {
     EvalArgs a;
-    fill_args(m, del_t, n, grad, stress_prev, stress, tangent, hprev, hcur, rows, hmask, flags, stress2, counters, emask_prev, emask, a);
-    const bool per_point = has_fields(m, fields);
+    fill_args(m, del_t, n, l, a);
+    const bool per_point = has_fields(m, l.fields);
     if (per_point) {  // (the twin is a measurement device of the scalar kernel)
         a.flags &= ~64;
         a.cache3d = nullptr;
         field_tables(m, a);
     }
     // only the plasticity laws count anything: skip the extra launch for the others
-    if ((reset_counters || counters) && law_counts(m->law)) HIP_TRY(hipMemsetAsync(a.counters, 0, kCounterBytes, stream));
+    if ((reset_counters || l.counters) && law_counts(m->law)) HIP_TRY(hipMemsetAsync(a.counters, 0, kCounterBytes, stream));
     if (n == 0) return FCAMD_OK;
     const int grid = grid_for(m, n);
     // the launchers report hipGetLastError(): drop whatever an earlier, unrelated call of this thread
@@ -502,7 +573,7 @@ int enqueue(fcamd_model* m, double del_t, int64_t n, const double* grad, const d
     (void)hipGetLastError();
     if (per_point) {
         FieldArgs f;
-        field_args_for(m, fields, field_p0, f);
+        field_args_for(m, l.fields, l.field_p0, f);
         HIP_TRY(launch_evaluate_fields(m->law, a, f, grid, stream));
         return FCAMD_OK;
     }
@@ -772,8 +843,7 @@ static int check_device_ex(fcamd_model* m, double del_t, int64_t n, const fcamd_
                            reinterpret_cast<const void* const*>(x->history_prev),
                            reinterpret_cast<const void* const*>(x->history), x->n_hist, x->flags);
     if (st != FCAMD_OK) return st;
-    if (x->flags & ~(FCAMD_EVAL_SPARSE_TANGENT | FCAMD_EVAL_SPLIT_HISTORY | FCAMD_EVAL_PACKED_HISTORY | FCAMD_EVAL_PARAM_FIELDS))
-        return fail(FCAMD_ERR_UNSUPPORTED, "unknown FCAMD_EVAL_* flag in 0x%x (2, FCAMD_EVAL_DELTA_HISTORY of ABI 0.3, was removed in 0.4)", x->flags);
+    // the device entries' own: the indexed form, fields, a device tangent under the sparse protocol
     if (x->parent_rows && m->constraint != FCAMD_FULL)
         return fail(FCAMD_ERR_UNSUPPORTED, "the indexed form exists for StressStrainConstraint.FULL only");
     if (has_fields(m, fields_of(x))) {
@@ -781,43 +851,11 @@ static int check_device_ex(fcamd_model* m, double del_t, int64_t n, const fcamd_
         st = check_fields(m, fields_of(x));
         if (st != FCAMD_OK) return st;
     }
-    if (x->history_mask && !has_sparse_history(m->law))
-        return fail(FCAMD_ERR_UNSUPPORTED, "sparse trial history exists for the plasticity laws only");
     if ((x->flags & FCAMD_EVAL_SPARSE_TANGENT) && (!x->history_mask || !x->tangent))
         return fail(FCAMD_ERR_BAD_ARG, "FCAMD_EVAL_SPARSE_TANGENT needs history_mask and tangent");
-    if ((x->flags & FCAMD_EVAL_PACKED_HISTORY) && n > 0) {
-        const bool split = (x->flags & FCAMD_EVAL_SPLIT_HISTORY) != 0 && has_split_history(m->law);
-        if (m->law != FCAMD_VON_MISES_3D && !split)
-            return fail(FCAMD_ERR_UNSUPPORTED, "FCAMD_EVAL_PACKED_HISTORY exists for VonMises3D and, with FCAMD_EVAL_SPLIT_HISTORY, for the "
-                                               "comfe-rs plasticity laws");
-        if (!x->history_mask || !x->packed_mask_prev || !x->packed_mask)
-            return fail(FCAMD_ERR_BAD_ARG, "FCAMD_EVAL_PACKED_HISTORY needs history_mask, packed_mask_prev and packed_mask");
-        if (x->parent_rows && m->law != FCAMD_VON_MISES_3D)
-            return fail(FCAMD_ERR_UNSUPPORTED, "FCAMD_EVAL_PACKED_HISTORY with parent_rows: VonMises3D only");
-        const int kd = split ? 1 : 0;
-        if (x->history[kd] == x->history_prev[kd] || x->packed_mask == x->packed_mask_prev)
-            return fail(FCAMD_ERR_BAD_ARG, "FCAMD_EVAL_PACKED_HISTORY needs trial plastic-strain and mask arrays of their own");
-    }
-    if (!aligned16(x->grad_del_u) || !aligned16(x->stress) || !aligned16(x->stress_prev) || !aligned16(x->tangent) || !aligned16(x->stress2))
+    if (!aligned16(x->grad_del_u) || !aligned16(x->tangent) || !aligned16(x->stress2))
         return fail(FCAMD_ERR_ALIGN, "device arrays must be 16-byte aligned");
-    for (int k = 0; k < x->n_hist; ++k)
-        if (!aligned16(x->history[k]) || !aligned16(x->history_prev[k]))
-            return fail(FCAMD_ERR_ALIGN, "device history arrays must be 16-byte aligned");
-    if (x->flags & FCAMD_EVAL_SPLIT_HISTORY) {
-        if (m->constraint != FCAMD_FULL) return fail(FCAMD_ERR_UNSUPPORTED, "FCAMD_EVAL_SPLIT_HISTORY: 3-D laws only");
-        if ((x->history[0] == x->history_prev[0]) != (x->history[1] == x->history_prev[1]))
-            return fail(FCAMD_ERR_BAD_ARG, "FCAMD_EVAL_SPLIT_HISTORY: both history arrays in place or both out of place");
-    }
-    return FCAMD_OK;
-}
-
-static int enqueue_ex(fcamd_model* m, double del_t, int64_t n, const fcamd_eval_args* x, hipStream_t stream, bool reset_counters) {
-    return enqueue(m, del_t, n, x->grad_del_u, x->stress_prev, x->stress, x->tangent, x->history_prev, x->history,
-                   stream, reset_counters, x->parent_rows, reinterpret_cast<unsigned long long*>(x->history_mask), x->flags,
-                   x->stress2, reinterpret_cast<unsigned long long*>(x->counters),
-                   (x->flags & FCAMD_EVAL_PACKED_HISTORY) ? reinterpret_cast<const unsigned long long*>(x->packed_mask_prev) : nullptr,
-                   (x->flags & FCAMD_EVAL_PACKED_HISTORY) ? reinterpret_cast<unsigned long long*>(x->packed_mask) : nullptr,
-                   fields_of(x), 0);
+    return check_protocol(m, n, x);
 }
 
 int fcamd_evaluate_device_ex(fcamd_model* m, double t, double del_t, int64_t n, const fcamd_eval_args* x) {
@@ -837,7 +875,7 @@ int fcamd_evaluate_device_ex(fcamd_model* m, double t, double del_t, int64_t n, 
     fcamd_context* c = m->ctx;
     HIP_TRY(hipSetDevice(c->device));
     if ((st = timing_begin(m)) != FCAMD_OK) return st;
-    st = enqueue_ex(m, del_t, n, x, c->stream, !m->timed);
+    st = enqueue(m, del_t, n, launch_of(m, x), c->stream, !m->timed);
     if (st != FCAMD_OK) return st;
     return timing_end(m);
 }
@@ -879,7 +917,7 @@ int fcamd_evaluate_batch(int count, fcamd_model* const* models, const int64_t* n
     // the others first, each with its own launch
     for (int k = 0; k < count; ++k) {
         if (n_small && batched(k)) continue;
-        const int st = enqueue_ex(models[k], del_t, n[k], &args[k], c->stream, true);
+        const int st = enqueue(models[k], del_t, n[k], launch_of(models[k], &args[k]), c->stream, true);
         if (st != FCAMD_OK) return st;
     }
     // tables of at most kBatchMax entries, the Drucker-Prager laws in tables of their own (their batch kernel is cut for 3 waves per
@@ -895,15 +933,9 @@ int fcamd_evaluate_batch(int count, fcamd_model* const* models, const int64_t* n
         for (; k < count && (int)tab.size() < fcamd_context::kBatchMax; ++k) {
             if (!batched(k) || fcamd::batch_law_is_dp(models[k]->law) != dp) continue;
             fcamd_model* m = models[k];
-            const fcamd_eval_args* x = &args[k];
             fcamd::BatchEntry e;
             memset(&e, 0, sizeof(e));  // (padding bytes too: the table is compared byte for byte)
-            const bool packed = (x->flags & FCAMD_EVAL_PACKED_HISTORY) != 0;
-            fcamd::fill_args(m, del_t, n[k], x->grad_del_u, x->stress_prev, x->stress, x->tangent, x->history_prev, x->history, x->parent_rows,
-                             reinterpret_cast<unsigned long long*>(x->history_mask), x->flags, x->stress2,
-                             reinterpret_cast<unsigned long long*>(x->counters),
-                             packed ? reinterpret_cast<const unsigned long long*>(x->packed_mask_prev) : nullptr,
-                             packed ? reinterpret_cast<unsigned long long*>(x->packed_mask) : nullptr, e.args);
+            fcamd::fill_args(m, del_t, n[k], launch_of(m, &args[k]), e.args);
             e.variant = fcamd::batch_variant_of(m->law, e.args);
             e.first_block = blocks;
             e.main_blocks = n[k] >= 64 ? grid_for(m, n[k]) : 0;

@@ -188,12 +188,30 @@ int validate_call(const fcamd_model* m, double del_t, int64_t n, const void* gra
 int enable_peer_access(fcamd_context* c, int peer_device);
 size_t ipc_safe_alloc_size(size_t bytes);
 
+// The arrays and the protocol of ONE evaluate launch, as addresses the device sees.  Value-initialised: nothing optional.
+struct Launch {
+    const double *grad = nullptr, *stress_prev = nullptr;
+    double *stress = nullptr, *stress2 = nullptr;  // stress2: second destination of the stress rows
+    double* tangent = nullptr;
+    const double* hist_prev[FCAMD_MAX_HISTORY] = {};
+    double* hist[FCAMD_MAX_HISTORY] = {};
+    const int* rows = nullptr;                                // parent_rows (the indexed form)
+    unsigned long long* hmask = nullptr;                      // sparse trial history: one ballot word per tile
+    const unsigned long long* emask_prev = nullptr;           // FCAMD_EVAL_PACKED_HISTORY: the EVER masks of the committed ...
+    unsigned long long *emask = nullptr, *counters = nullptr;  // ... and the trial array; caller-owned counters instead of the model's
+    const double* const* fields = nullptr;                    // per-point parameter fields (FCAMD_EVAL_PARAM_FIELDS) ...
+    int64_t field_p0 = 0;                                     // ... read from this point on
+    int flags = 0;                                            // FCAMD_EVAL_* (and the library-internal kFlagTangentParamsHost)
+};
+// the launch a caller's fcamd_eval_args describe (already validated); the packed masks only under FCAMD_EVAL_PACKED_HISTORY
+Launch launch_of(const fcamd_model* m, const fcamd_eval_args* x);
+// the same launch from point p0 on (a multiple of 64: whole tiles, whole mask words): the one place that knows how far `p0` points
+// are in each array.  Null members stay null; a member that lives in a chunk-local buffer is assigned after slicing.
+Launch slice(const fcamd_model* m, const Launch& l, int64_t p0);
+// the refusals every entry that takes fcamd_eval_args shares (flags, sparse / packed / split history, alignment of the state arrays)
+int check_protocol(const fcamd_model* m, int64_t n, const fcamd_eval_args* x);
 // one evaluate launch of `n` points on `stream` (fcamd_capi.cpp)
-int enqueue(fcamd_model* m, double del_t, int64_t n, const double* grad, const double* stress_prev, double* stress,
-            double* tangent, const double* const* hprev, double* const* hcur, hipStream_t stream, bool reset_counters,
-            const int* rows = nullptr, unsigned long long* hmask = nullptr, int flags = 0, double* stress2 = nullptr,
-            unsigned long long* counters = nullptr, const unsigned long long* emask_prev = nullptr,
-            unsigned long long* emask = nullptr, const double* const* fields = nullptr, int64_t field_p0 = 0);
+int enqueue(fcamd_model* m, double del_t, int64_t n, const Launch& l, hipStream_t stream, bool reset_counters);
 // per-point parameter fields (FCAMD_EVAL_PARAM_FIELDS): are there any, are they allowed for this model and form?
 // the field table of a call (FCAMD_EVAL_PARAM_FIELDS: it travels in stress_3d), or NULL
 const double* const* fields_of(const fcamd_eval_args* x);

@@ -528,8 +528,8 @@ void host_tangent_done(fcamd_context* c, ExpandPool* pool) {
 }
 
 // Constant tangent: ONE launch without a tangent array while the pool fills the caller's array from the law's table.
-template <class Launch>
-int run_const_tangent(fcamd_model* m, ExpandPool* pool, int64_t n, double* tangent, fcamd_stats* stats, Launch&& launch) {
+template <class LaunchFn>
+int run_const_tangent(fcamd_model* m, ExpandPool* pool, int64_t n, double* tangent, fcamd_stats* stats, LaunchFn&& launch) {
     fcamd_context* c = m->ctx;
     pool_begin(pool, host_tangent_job(m, tangent));  // (the tables of m were brought up to date for this del_t by the caller)
     pool_post(pool, 0, n, nullptr, nullptr);
@@ -544,8 +544,8 @@ int run_const_tangent(fcamd_model* m, ExpandPool* pool, int64_t n, double* tange
 // ballot into a ring of page-locked chunks (kFlagTangentParams); the pool expands chunk k while the GPU works on the chunks behind it.
 // `launch(p0, np, params, stream)` enqueues the kernel of one chunk.  All HIP calls stay on the calling thread: it posts a chunk to
 // the pool when the chunk's event has completed and reuses a slot when the pool has expanded what the slot held.
-template <class Launch>
-int run_param_chunks(fcamd_model* m, ExpandPool* pool, int64_t n, double* tangent, fcamd_stats* stats, Launch&& launch) {
+template <class LaunchFn>
+int run_param_chunks(fcamd_model* m, ExpandPool* pool, int64_t n, double* tangent, fcamd_stats* stats, LaunchFn&& launch) {
     fcamd_context* c = m->ctx;
     // the chunks, their tapered tail and the ring's slots: host_tangent_plan
     const HostTangentJob job = host_tangent_job(m, tangent);
@@ -615,6 +615,20 @@ int run_param_chunks(fcamd_model* m, ExpandPool* pool, int64_t n, double* tangen
     else st = finish_chunks(m, stats, /*downloaded=*/true);
     host_tangent_done(c, pool);
     return st;
+}
+
+// The call `whole` (everything but its tangent) with the tangent rows rebuilt by the pool: one launch without a tangent array, or
+// the launches of the parameter pipeline, each a slice of the call that writes its parameters into the ring slot `params`.
+int run_host_tangent(fcamd_model* m, ExpandPool* pool, double del_t, int64_t n, const Launch& whole, double* tangent, fcamd_stats* stats) {
+    constants_for_call(m, del_t);
+    auto launch = [&](int64_t p0, int64_t np, double* params, hipStream_t on) {
+        Launch l = slice(m, whole, p0);
+        l.tangent = params;
+        if (params) l.flags |= kFlagTangentParamsHost;
+        return enqueue(m, del_t, np, l, on, false);
+    };
+    if (host_tangent_kind(m) == 1 + HostTangentJob::CONST) return run_const_tangent(m, pool, n, tangent, stats, launch);
+    return run_param_chunks(m, pool, n, tangent, stats, launch);
 }
 
 }  // namespace
@@ -691,19 +705,20 @@ int fcamd_evaluate_host(fcamd_model* m, double t, double del_t, int64_t n, const
         if (st != FCAMD_OK) return st;
         hipStream_t s = c->hstream[0];
         if (has_sparse_history(m->law)) HIP_TRY(hipMemsetAsync(m->d_counters, 0, kCounterBytes, s));
+        Launch b;  // every array of a chunk lies in the scratch, in place
+        b.grad = reinterpret_cast<const double*>(c->bounce_dev + o_grad);
+        b.stress_prev = b.stress = reinterpret_cast<double*>(c->bounce_dev + o_stress);
+        b.tangent = tangent ? reinterpret_cast<double*>(c->bounce_dev + o_tan) : nullptr;
+        for (int k = 0; k < NH; ++k) b.hist_prev[k] = b.hist[k] = reinterpret_cast<double*>(c->bounce_dev + o_hist[k]);
         for (int64_t p0 = 0; p0 < n; p0 += chunk) {
             const size_t np = (size_t)std::min<int64_t>(chunk, n - p0);
             std::memcpy(c->bounce + o_grad, grad + GD2 * p0, np * GD2 * sizeof(double));
             std::memcpy(c->bounce + o_stress, stress + SD * p0, np * SD * sizeof(double));
-            double* d_hist[FCAMD_MAX_HISTORY] = {nullptr, nullptr};
             for (int k = 0; k < NH; ++k) {
                 const size_t d = (size_t)m->info.hist[k].dim;
                 std::memcpy(c->bounce + o_hist[k], hist[k] + d * p0, np * d * sizeof(double));
-                d_hist[k] = reinterpret_cast<double*>(c->bounce_dev + o_hist[k]);
             }
-            double* d_stress = reinterpret_cast<double*>(c->bounce_dev + o_stress);
-            st = enqueue(m, del_t, (int64_t)np, reinterpret_cast<const double*>(c->bounce_dev + o_grad), d_stress, d_stress,
-                         tangent ? reinterpret_cast<double*>(c->bounce_dev + o_tan) : nullptr, d_hist, d_hist, s, false);
+            st = enqueue(m, del_t, (int64_t)np, b, s, false);
             if (st != FCAMD_OK) return drain_and_return(c, st);
             if (p0 + chunk >= n && has_sparse_history(m->law))  // last chunk: the counters ride on the same wait
                 HIP_TRY_DRAIN(c, hipMemcpyAsync(m->h_counters, m->d_counters, kCounterBytes, hipMemcpyDeviceToHost, s));
@@ -729,20 +744,14 @@ int fcamd_evaluate_host(fcamd_model* m, double t, double del_t, int64_t n, const
         c->last_host_mode |= FCAMD_HOST_ZERO_COPY_IN | FCAMD_HOST_ZERO_COPY_OUT;
         hipStream_t s = c->hstream[0];
         if (has_sparse_history(m->law)) HIP_TRY(hipMemsetAsync(m->d_counters, 0, kCounterBytes, s));
-        double* zh[FCAMD_MAX_HISTORY] = {reinterpret_cast<double*>(z_hist[0]), reinterpret_cast<double*>(z_hist[1])};
-        double* zs = reinterpret_cast<double*>(z_stress);
-        if (pool) {  // the kernel works on the other arrays in place; the tangent rows are the CPU's (fcamd_hosttangent.cpp)
-            constants_for_call(m, del_t);
-            auto launch = [&](int64_t p0, int64_t np, double* params, hipStream_t on) {
-                double* h[FCAMD_MAX_HISTORY] = {nullptr, nullptr};
-                for (int k = 0; k < NH; ++k) h[k] = zh[k] + (size_t)m->info.hist[k].dim * p0;
-                return enqueue(m, del_t, np, reinterpret_cast<const double*>(z_grad) + GD2 * p0, zs + SD * p0, zs + SD * p0, params, h, h, on,
-                               false, nullptr, nullptr, params ? kFlagTangentParamsHost : 0);
-            };
-            if (host_tangent_kind(m) == 1 + HostTangentJob::CONST) return run_const_tangent(m, pool, n, tangent, stats, launch);
-            return run_param_chunks(m, pool, n, tangent, stats, launch);
-        }
-        st = enqueue(m, del_t, n, reinterpret_cast<const double*>(z_grad), zs, zs, reinterpret_cast<double*>(z_tan), zh, zh, s, false);
+        Launch z;  // the caller's arrays, in place
+        z.grad = reinterpret_cast<const double*>(z_grad);
+        z.stress_prev = z.stress = reinterpret_cast<double*>(z_stress);
+        z.tangent = reinterpret_cast<double*>(z_tan);
+        for (int k = 0; k < NH; ++k) z.hist_prev[k] = z.hist[k] = reinterpret_cast<double*>(z_hist[k]);
+        // the kernel works on the other arrays in place; the tangent rows are the CPU's (fcamd_hosttangent.cpp)
+        if (pool) return run_host_tangent(m, pool, del_t, n, z, tangent, stats);
+        st = enqueue(m, del_t, n, z, s, false);
         if (st != FCAMD_OK) return drain_and_return(c, st);
         return finish_single_stream(m, stats);
     }
@@ -764,10 +773,13 @@ int fcamd_evaluate_host(fcamd_model* m, double t, double del_t, int64_t n, const
         double* d_grad = c->dchunk[slot];
         double* d_stress = d_grad + 10 * c->dchunk_points;  // slots sized for FULL (9 -> 10: keeps 16-B alignment)
         double* d_tan = d_stress + 6 * c->dchunk_points;
-        double* d_hist[FCAMD_MAX_HISTORY] = {nullptr, nullptr};
+        Launch l;  // every array of the chunk lies in the slot, in place
+        l.grad = d_grad;
+        l.stress_prev = l.stress = d_stress;
+        l.tangent = tangent ? d_tan : nullptr;
         double* cur = d_tan + 36 * c->dchunk_points;
         for (int k = 0; k < NH; ++k) {
-            d_hist[k] = cur;
+            l.hist_prev[k] = l.hist[k] = cur;
             cur += (size_t)m->info.hist[k].dim * c->dchunk_points;
             // keep 16-byte alignment for odd per-point dimensions (alpha: 1, comfe history: 7)
             if ((reinterpret_cast<uintptr_t>(cur) & 15u) != 0) cur += 1;
@@ -776,16 +788,16 @@ int fcamd_evaluate_host(fcamd_model* m, double t, double del_t, int64_t n, const
         HIP_TRY_DRAIN(c, hipMemcpyAsync(d_stress, stress + SD * p0, (size_t)np * SD * sizeof(double), hipMemcpyHostToDevice, s));
         for (int k = 0; k < NH; ++k) {
             const size_t d = (size_t)m->info.hist[k].dim;
-            HIP_TRY_DRAIN(c, hipMemcpyAsync(d_hist[k], hist[k] + d * p0, (size_t)np * d * sizeof(double), hipMemcpyHostToDevice, s));
+            HIP_TRY_DRAIN(c, hipMemcpyAsync(l.hist[k], hist[k] + d * p0, (size_t)np * d * sizeof(double), hipMemcpyHostToDevice, s));
         }
-        st = enqueue(m, del_t, np, d_grad, d_stress, d_stress, tangent ? d_tan : nullptr, d_hist, d_hist, s, false);
+        st = enqueue(m, del_t, np, l, s, false);
         if (st != FCAMD_OK) return drain_and_return(c, st);
         HIP_TRY_DRAIN(c, hipMemcpyAsync(stress + SD * p0, d_stress, (size_t)np * SD * sizeof(double), hipMemcpyDeviceToHost, s));
         if (tangent)
             HIP_TRY_DRAIN(c, hipMemcpyAsync(tangent + TD * p0, d_tan, (size_t)np * TD * sizeof(double), hipMemcpyDeviceToHost, s));
         for (int k = 0; k < NH; ++k) {
             const size_t d = (size_t)m->info.hist[k].dim;
-            HIP_TRY_DRAIN(c, hipMemcpyAsync(hist[k] + d * p0, d_hist[k], (size_t)np * d * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIP_TRY_DRAIN(c, hipMemcpyAsync(hist[k] + d * p0, l.hist[k], (size_t)np * d * sizeof(double), hipMemcpyDeviceToHost, s));
         }
     }
     return finish_chunks(m, stats);
@@ -798,45 +810,17 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
     if (x->parent_rows || x->stress2 || x->tangent || x->wrapper_constraint)
         return fail(FCAMD_ERR_UNSUPPORTED, "fcamd_evaluate_resident: parent_rows / stress2 / a device tangent / the wrapper form are options of fcamd_evaluate_device_ex");
     const double* grad = x->grad_del_u;  // HOST array
-    const double* stress_prev = x->stress_prev;
-    double* stress = x->stress;
-    const double* const* hist_prev = x->history_prev;
-    double* const* hist = x->history;
-    const int n_hist = x->n_hist, flags = x->flags;
-    uint64_t* history_mask = x->history_mask;
-    const bool packed = (flags & FCAMD_EVAL_PACKED_HISTORY) != 0;
-    const unsigned long long* emask_prev = packed ? reinterpret_cast<const unsigned long long*>(x->packed_mask_prev) : nullptr;
-    unsigned long long* emask = packed ? reinterpret_cast<unsigned long long*>(x->packed_mask) : nullptr;
-    int st = validate_call(m, del_t, n, grad, stress_prev, stress,
-                           reinterpret_cast<const void* const*>(hist_prev),
-                           reinterpret_cast<const void* const*>(hist), n_hist, flags);
+    const int flags = x->flags;
+    int st = validate_call(m, del_t, n, grad, x->stress_prev, x->stress, reinterpret_cast<const void* const*>(x->history_prev),
+                           reinterpret_cast<const void* const*>(x->history), x->n_hist, flags);
     if (st != FCAMD_OK) return st;
-    if (history_mask && !has_sparse_history(m->law))
-        return fail(FCAMD_ERR_UNSUPPORTED, "sparse trial history exists for the plasticity laws only");
-    if (flags & ~(FCAMD_EVAL_SPARSE_TANGENT | FCAMD_EVAL_SPLIT_HISTORY | FCAMD_EVAL_PACKED_HISTORY | FCAMD_EVAL_PARAM_FIELDS))
-        return fail(FCAMD_ERR_UNSUPPORTED, "unknown FCAMD_EVAL_* flag in 0x%x (2, FCAMD_EVAL_DELTA_HISTORY of ABI 0.3, was removed in 0.4)", flags);
-    if (packed && n > 0) {  // as fcamd_evaluate_device_ex
-        if (!history_mask || !emask_prev || !emask || emask == emask_prev)
-            return fail(FCAMD_ERR_BAD_ARG, "FCAMD_EVAL_PACKED_HISTORY needs history_mask and two mask arrays, packed_mask_prev and packed_mask");
-        if (m->law != FCAMD_VON_MISES_3D && !((flags & FCAMD_EVAL_SPLIT_HISTORY) && has_split_history(m->law)))
-            return fail(FCAMD_ERR_UNSUPPORTED, "FCAMD_EVAL_PACKED_HISTORY: VonMises3D, or a comfe-rs plasticity law with FCAMD_EVAL_SPLIT_HISTORY");
-        const int kd = (flags & FCAMD_EVAL_SPLIT_HISTORY) ? 1 : 0;
-        if (hist && hist_prev && hist[kd] == hist_prev[kd])
-            return fail(FCAMD_ERR_BAD_ARG, "FCAMD_EVAL_PACKED_HISTORY needs a trial plastic-strain array of its own");
-    }
-    if (!aligned16(stress) || !aligned16(stress_prev))
-        return fail(FCAMD_ERR_ALIGN, "device arrays must be 16-byte aligned");
-    // per-point parameter fields (device arrays of n doubles): every launch below takes them at its first point
-    const double* const* fields = has_fields(m, fields_of(x)) ? fields_of(x) : nullptr;
-    if ((st = check_fields(m, fields)) != FCAMD_OK) return st;
-    // history arrays of the state: the law's fields, or -- FCAMD_EVAL_SPLIT_HISTORY -- [scalar (n), eps_p rows (6 n)]
-    const bool split = (flags & FCAMD_EVAL_SPLIT_HISTORY) != 0;
-    const int NH = split ? 2 : m->info.n_hist;
-    size_t hdim[FCAMD_MAX_HISTORY] = {0, 0};
-    for (int k = 0; k < NH; ++k) hdim[k] = split ? (k == 0 ? 1 : 6) : (size_t)m->info.hist[k].dim;
-    for (int k = 0; k < NH; ++k)
-        if (!aligned16(hist[k]) || !aligned16(hist_prev[k]))
-            return fail(FCAMD_ERR_ALIGN, "device history arrays must be 16-byte aligned");
+    if ((st = check_protocol(m, n, x)) != FCAMD_OK) return st;
+    // The state's side of the whole call: device arrays, masks, per-point parameter fields (device arrays of n doubles), flags.  The
+    // host side -- gradient, tangent, second stress store -- is filled in by the path the call takes; every launch is a slice of it.
+    Launch L = launch_of(m, x);
+    L.grad = nullptr;
+    L.counters = nullptr;  // the host entries count into the model's own counters and report them (stats)
+    if ((st = check_fields(m, L.fields)) != FCAMD_OK) return st;
     fcamd_context* c = m->ctx;
     std::lock_guard<std::recursive_mutex> lock(c->host_mu);
     HostTimer timer(m);
@@ -856,7 +840,7 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
     // they are in the caller's array, and for the 3-D laws' one-launch pass only
     ExpandPool* pool = host_tangent_for(m, n, tangent_host);
     if ((flags & FCAMD_EVAL_SPARSE_TANGENT) || m->dims.gdim != 3) pool = nullptr;
-    if (fields) pool = nullptr;  // the host threads tile ONE tangent: with fields every point has its own, the kernel writes them
+    if (L.fields) pool = nullptr;  // the host threads tile ONE tangent: with fields every point has its own, the kernel writes them
     const bool all_registered = mapped(c, grad, N * GD2 * sizeof(double)) &&
                                 (!stress_host || mapped(c, stress_host, N * SD * sizeof(double))) &&
                                 (pool || !tangent_host || mapped(c, tangent_host, N * TD * sizeof(double)));
@@ -888,22 +872,15 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
         for (int64_t p0 = 0; p0 < n; p0 += chunk) {
             const size_t np = (size_t)std::min<int64_t>(chunk, n - p0);
             std::memcpy(c->bounce + o_grad, grad + GD2 * p0, np * GD2 * sizeof(double));
-            const double* hp[FCAMD_MAX_HISTORY] = {nullptr, nullptr};
-            double* hc[FCAMD_MAX_HISTORY] = {nullptr, nullptr};
-            for (int k = 0; k < NH; ++k) {
-                const size_t d = hdim[k];
-                hp[k] = hist_prev[k] + d * p0;
-                hc[k] = hist[k] + d * p0;
-            }
-            // the scratch holds no previous tangent: every row is written (no sparse tangent)
-            st = enqueue(m, del_t, (int64_t)np, reinterpret_cast<const double*>(c->bounce_dev + o_grad), stress_prev + SD * p0,
-                         stress + SD * p0, tangent_host ? reinterpret_cast<double*>(c->bounce_dev + o_tan) : nullptr, hp, hc, s, false,
-                         nullptr, history_mask ? reinterpret_cast<unsigned long long*>(history_mask) + p0 / 64 : nullptr,
-                         flags & ~FCAMD_EVAL_SPARSE_TANGENT, second_store ? reinterpret_cast<double*>(c->bounce_dev + o_stress) : nullptr,
-                         nullptr, emask_prev ? emask_prev + p0 / 64 : nullptr, emask ? emask + p0 / 64 : nullptr, fields, p0);
+            Launch l = slice(m, L, p0);
+            l.grad = reinterpret_cast<const double*>(c->bounce_dev + o_grad);
+            if (tangent_host) l.tangent = reinterpret_cast<double*>(c->bounce_dev + o_tan);
+            if (second_store) l.stress2 = reinterpret_cast<double*>(c->bounce_dev + o_stress);
+            l.flags = flags & ~FCAMD_EVAL_SPARSE_TANGENT;  // the scratch holds no previous tangent: every row is written
+            st = enqueue(m, del_t, (int64_t)np, l, s, false);
             if (st != FCAMD_OK) return drain_and_return(c, st);
             if (stress_host && !second_store)
-                HIP_TRY_DRAIN(c, hipMemcpyAsync(c->bounce + o_stress, stress + SD * p0, np * SD * sizeof(double), hipMemcpyDeviceToHost, s));
+                HIP_TRY_DRAIN(c, hipMemcpyAsync(c->bounce + o_stress, l.stress, np * SD * sizeof(double), hipMemcpyDeviceToHost, s));
             if (p0 + chunk >= n && has_sparse_history(m->law))  // last chunk: the counters ride on the same wait
                 HIP_TRY_DRAIN(c, hipMemcpyAsync(m->h_counters, m->d_counters, kCounterBytes, hipMemcpyDeviceToHost, s));
             HIP_TRY_DRAIN(c, hipStreamSynchronize(s));
@@ -924,26 +901,14 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
     if (z_grad && (z_tan || !tangent_host || pool) && (z_stress || !stress_host) && m->dims.gdim == 3) {
         hipStream_t s = c->hstream[0];
         if (has_sparse_history(m->law)) HIP_TRY(hipMemsetAsync(m->d_counters, 0, kCounterBytes, s));
+        L.grad = z_grad;
+        L.stress2 = z_stress;
         if (pool) {  // state on the device, gradient and stress over the link in place, the tangent rows from the CPU
             if (z_stress) c->last_host_mode |= FCAMD_HOST_ZERO_COPY_OUT;  // (the stress is the kernel's own store into the caller's array)
-            constants_for_call(m, del_t);
-            auto launch = [&](int64_t p0, int64_t np, double* params, hipStream_t on) {
-                const double* hp[FCAMD_MAX_HISTORY] = {nullptr, nullptr};
-                double* hc[FCAMD_MAX_HISTORY] = {nullptr, nullptr};
-                for (int k = 0; k < NH; ++k) {
-                    hp[k] = hist_prev[k] + hdim[k] * p0;
-                    hc[k] = hist[k] + hdim[k] * p0;
-                }
-                return enqueue(m, del_t, np, z_grad + GD2 * p0, stress_prev + SD * p0, stress + SD * p0, params, hp, hc, on, false, nullptr,
-                               history_mask ? reinterpret_cast<unsigned long long*>(history_mask) + p0 / 64 : nullptr,
-                               flags | (params ? kFlagTangentParamsHost : 0), z_stress ? z_stress + SD * p0 : nullptr, nullptr,
-                               emask_prev ? emask_prev + p0 / 64 : nullptr, emask ? emask + p0 / 64 : nullptr);
-            };
-            if (host_tangent_kind(m) == 1 + HostTangentJob::CONST) return run_const_tangent(m, pool, n, tangent_host, stats, launch);
-            return run_param_chunks(m, pool, n, tangent_host, stats, launch);
+            return run_host_tangent(m, pool, del_t, n, L, tangent_host, stats);
         }
-        st = enqueue(m, del_t, n, z_grad, stress_prev, stress, z_tan, hist_prev, hist, s, false, nullptr,
-                     reinterpret_cast<unsigned long long*>(history_mask), flags, z_stress, nullptr, emask_prev, emask, fields, 0);
+        L.tangent = z_tan;
+        st = enqueue(m, del_t, n, L, s, false);
         if (st != FCAMD_OK) return drain_and_return(c, st);
         return finish_single_stream(m, stats);
     }
@@ -953,34 +918,27 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
     const int nslots = c->opt.host_slots;
     HIP_TRY(hipMemsetAsync(m->d_counters, 0, kCounterBytes, c->hstream[0]));
     HIP_TRY(hipStreamSynchronize(c->hstream[0]));
+    // page-locked, GPU-mapped caller arrays are read / written by the kernel itself (zero copy); the others go through the slot
+    L.grad = z_grad;
+    L.tangent = z_tan;
+    if (!z_tan) L.flags &= ~FCAMD_EVAL_SPARSE_TANGENT;  // the staging buffer of a chunk holds no previous tangent: full rows
     int slot = 0;
     for (int64_t p0 = 0; p0 < n; p0 += chunk, slot = (slot + 1) % nslots) {
         const int64_t np = std::min<int64_t>(chunk, n - p0);
         hipStream_t s = c->hstream[slot];
         double* d_grad = c->dchunk[slot];  // unused (possibly null) when gradient and tangent are zero copy
         double* d_tan = d_grad ? d_grad + 10 * c->dchunk_points : nullptr;
-        // chunk offsets are multiples of 64 points: every sub-array stays 16-byte aligned and the
-        // per-tile mask words line up
-        const double* hp[FCAMD_MAX_HISTORY] = {nullptr, nullptr};
-        double* hc[FCAMD_MAX_HISTORY] = {nullptr, nullptr};
-        for (int k = 0; k < NH; ++k) {
-            const size_t d = hdim[k];
-            hp[k] = hist_prev[k] + d * p0;
-            hc[k] = hist[k] + d * p0;
-        }
-        // page-locked, GPU-mapped caller arrays are read / written by the kernel itself (zero copy)
-        const double* k_grad = z_grad ? z_grad + GD2 * p0 : d_grad;
-        double* k_tan = !tangent_host ? nullptr : (z_tan ? z_tan + TD * p0 : d_tan);
-        if (!z_grad)
+        // chunk offsets are multiples of 64 points: every sub-array stays 16-byte aligned and the per-tile mask words line up
+        Launch l = slice(m, L, p0);
+        if (!z_grad) {
+            l.grad = d_grad;
             HIP_TRY_DRAIN(c, hipMemcpyAsync(d_grad, grad + GD2 * p0, (size_t)np * GD2 * sizeof(double), hipMemcpyHostToDevice, s));
-        st = enqueue(m, del_t, np, k_grad, stress_prev + SD * p0, stress + SD * p0, k_tan,
-                     hp, hc, s, false, nullptr,
-                     history_mask ? reinterpret_cast<unsigned long long*>(history_mask) + p0 / 64 : nullptr,
-                     z_tan ? flags : (flags & ~FCAMD_EVAL_SPARSE_TANGENT),  // the staging buffer of a chunk holds no previous tangent: full rows
-                     nullptr, nullptr, emask_prev ? emask_prev + p0 / 64 : nullptr, emask ? emask + p0 / 64 : nullptr, fields, p0);
+        }
+        if (tangent_host && !z_tan) l.tangent = d_tan;
+        st = enqueue(m, del_t, np, l, s, false);
         if (st != FCAMD_OK) return drain_and_return(c, st);
         if (stress_host)
-            HIP_TRY_DRAIN(c, hipMemcpyAsync(stress_host + SD * p0, stress + SD * p0, (size_t)np * SD * sizeof(double),
+            HIP_TRY_DRAIN(c, hipMemcpyAsync(stress_host + SD * p0, l.stress, (size_t)np * SD * sizeof(double),
                                             hipMemcpyDeviceToHost, s));
         if (tangent_host && !z_tan)
             HIP_TRY_DRAIN(c, hipMemcpyAsync(tangent_host + TD * p0, d_tan, (size_t)np * TD * sizeof(double),

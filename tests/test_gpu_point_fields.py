@@ -98,13 +98,13 @@ def run_resident(law, gs, n, **kw):
     return st.stress.clone(), st.tangent.clone(), None if h is None else {k: v.clone() for k, v in h.items()}
 
 
-def run_resident_into(law, gs, n):
+def run_resident_into(law, gs, n, after_call=lambda stats: None):
     """the host assembler's form: NumPy gradient in, the trial stress / tangent into NumPy arrays (fcamd_evaluate_resident)"""
     st = ResidentState(law, n)
     s, t = np.zeros(6 * n), np.zeros(36 * n)
     for k, g in enumerate(gs):
-        st.evaluate_into(0.0, 1.0, 0.5 * g, s, t)
-        st.evaluate_into(0.0, 1.0, g, s, t)
+        after_call(st.evaluate_into(0.0, 1.0, 0.5 * g, s, t))
+        after_call(st.evaluate_into(0.0, 1.0, g, s, t))
         if k < len(gs) - 1:
             st.update()
     h = st.history
@@ -150,6 +150,35 @@ def test_constant_field_equals_scalar(name, n):
     # one field among scalars
     one = make(name, dict(scal, **{LAWS[name][2][-1]: np.full(n, float(scal[LAWS[name][2][-1]]))}))
     compare_runs(run_in_place(one, gs, n, False), run_in_place(ref, gs, n, False), f"{name} one field")
+
+
+# --- 1b. the chunked pass of fcamd_evaluate_resident takes every chunk's fields at the chunk's first point -----------
+@pytest.mark.parametrize("name", ["LinearElasticityModel", "VonMises3D"])
+def test_fields_through_the_chunked_resident_pass(name):
+    """n = 357 (five tiles and a ragged tail of 37) in chunks of 128 points -- the fields of the three launches start at points 0, 128
+    and 256 -- gives the bits of the default path's single launch.  The fields differ at every point: a chunk that read them from a
+    wrong offset would change every value of the chunk."""
+    n = 357
+    p = random_fields(name, n, np.random.default_rng(13))
+    assert all(np.unique(v).size == n for v in p.values() if isinstance(v, np.ndarray))
+    law = make(name, p)
+    gs = [3.0 * g for g in grads(n, 17)]
+    ref = run_resident_into(law, gs, n)
+    ctx = law._handle(_capi.default_device()).ctx
+    modes, plastic = [], []
+
+    def after_call(stats):
+        modes.append(ctx.last_host_mode())
+        plastic.append(stats.n_plastic)
+
+    ctx.set_option("bounce_max", 0), ctx.set_option("zero_copy", 0), ctx.set_option("host_chunk", 128)
+    try:
+        got = run_resident_into(law, gs, n, after_call)
+    finally:
+        ctx.set_option("bounce_max", 256 << 10), ctx.set_option("zero_copy", 1), ctx.set_option("host_chunk", 0)
+    assert modes == [_capi.HOST_TEMP_LOCK] * (2 * len(gs)), modes
+    assert name != "VonMises3D" or max(plastic) > 0
+    compare_runs(got, ref, f"{name} chunked evaluate_into")
 
 
 # --- 2. scattered parameter groups are one scalar law per group, bit for bit -------------------------------------

@@ -369,10 +369,11 @@ def test_resident_scratch_path_in_chunks(kind, request):
                 a.update(), b.update()
 
 
-@pytest.mark.parametrize("kind", ["von_mises_3d", "linear_elasticity"])
+@pytest.mark.parametrize("kind", ["von_mises_3d", "linear_elasticity", "comfe_mises_plasticity"])
 def test_resident_chunked_dma_pipeline(kind):
     """Option "zero_copy" = 0: fcamd_evaluate_resident page-locks the pageable host arrays and moves them chunk by chunk
-    by DMA through the four slots (here 13 chunks of 16 384 points) -- same numbers as the one-launch pass."""
+    by DMA through the four slots (here 13 chunks of 16 384 points) -- same numbers as the one-launch pass.  The comfe-rs Mises
+    law keeps its state in the split, packed layout: every chunk takes its [1, 6] history rows and its mask words at its own offset."""
     n = 200_003
     p, g, s, h = random_case(kind, n, seed=29)
     law = make_law(kind, p)
@@ -384,17 +385,21 @@ def test_resident_chunked_dma_pipeline(kind):
         gi = g * scale
         ctx.set_option("zero_copy", 0), ctx.set_option("host_chunk", 16384)
         try:
-            a.evaluate_into(0.0, 1.0, gi, sa, ta)
+            stats = a.evaluate_into(0.0, 1.0, gi, sa, ta)
             assert data_path(ctx) == TEMP
         finally:
             ctx.set_option("zero_copy", 1), ctx.set_option("host_chunk", 0)
         b.evaluate_into(0.0, 1.0, gi, sb, tb)
         # (linear elasticity: the constant tangent is written by the first call only, later ones do not pass the array)
-        assert data_path(ctx) == ((ZC | TEMP) if kind == "von_mises_3d" or it == 0 else (_capi.HOST_ZERO_COPY_IN | TEMP))
+        assert data_path(ctx) == ((ZC | TEMP) if kind != "linear_elasticity" or it == 0 else (_capi.HOST_ZERO_COPY_IN | TEMP))
         assert np.array_equal(sa, sb), it
-        if kind == "von_mises_3d" or it == 0:
+        if kind != "linear_elasticity" or it == 0:
             assert np.array_equal(ta, tb), it
         assert torch.equal(a.stress, b.stress)
+        for k in (h or {}):
+            assert torch.equal(a.history[k], b.history[k]), (it, k)
+        if kind == "comfe_mises_plasticity":
+            assert a._split and a._packed and stats.n_plastic > 0
         a.update(), b.update()
 
 
