@@ -147,24 +147,19 @@ __device__ __forceinline__ void user_tangent(const UserArgs& a, const UserParams
     if constexpr (kPasses == 1) user_out<36, FULL, NT>(D, region, lane, a.tangent + p0 * 36, npts * 36);
 }
 
-template <bool FULL, bool NT>
-__device__ __forceinline__ unsigned long long user_tile(const UserArgs& a, const UserParams& p, double* region, long long p0,
-                                                        int npts, int lane) {
-    double g[9], s[6], e[6];
-    UserHistoryT<double> h;
-    user_tile_in<FULL, NT>(a, region, p0, npts, lane, g, s, e, h);
-    const bool live = FULL || lane < npts;
-    const int max_iter = (int)a.params[FCAMD_USER_IM_SLOT];
-    const double tol = a.params[FCAMD_USER_IM_SLOT + 1];
-
-    double x[kN];
-    const int code = fcamd_user_start<double>(p, a.t, a.del_t, e, s, h, x);
-    const bool solved = live && code == 1;  // the lanes whose x comes out of the Newton loop
+// start<double> and the Newton loop of one tile: x on return.  `live`: the lanes whose points count (the others never iterate).
+// `solved`: the lanes whose x came out of the loop; returns whether the lane's point did not converge.  Wave-collective: the loop
+// runs while a ballot of the lanes still iterating is non-zero.
+__device__ __forceinline__ bool user_newton(const UserParams& p, double t, double del_t, const double (&e)[6], const double (&s)[6],
+                                            const UserHistoryT<double>& h, bool live, int max_iter, double tol, double (&x)[kN],
+                                            bool& solved) {
+    const int code = fcamd_user_start<double>(p, t, del_t, e, s, h, x);
+    solved = live && code == 1;  // the lanes whose x comes out of the Newton loop
     bool failed = code != 0 && code != 1;
     bool active = solved;
     for (int it = 0; __builtin_amdgcn_ballot_w64(active) != 0ull; ++it) {
         double r[kN], J[kN * kN];
-        user_jacobian(p, a.t, a.del_t, e, s, h, x, r, J);
+        user_jacobian(p, t, del_t, e, s, h, x, r, J);
         bool conv = true;
 #pragma unroll
         for (int i = 0; i < kN; ++i) conv = conv && __builtin_fabs(r[i]) <= tol;  // false for a NaN
@@ -179,6 +174,22 @@ __device__ __forceinline__ unsigned long long user_tile(const UserArgs& a, const
         }
         active = step;
     }
+    return failed;
+}
+
+template <bool FULL, bool NT>
+__device__ __forceinline__ unsigned long long user_tile(const UserArgs& a, const UserParams& p, double* region, long long p0,
+                                                        int npts, int lane) {
+    double g[9], s[6], e[6];
+    UserHistoryT<double> h;
+    user_tile_in<FULL, NT>(a, region, p0, npts, lane, g, s, e, h);
+    const bool live = FULL || lane < npts;
+    const int max_iter = (int)a.params[FCAMD_USER_IM_SLOT];
+    const double tol = a.params[FCAMD_USER_IM_SLOT + 1];
+
+    double x[kN];
+    bool solved;
+    const bool failed = user_newton(p, a.t, a.del_t, e, s, h, live, max_iter, tol, x, solved);
     const unsigned long long bad = __builtin_amdgcn_ballot_w64(live && failed);
 
     {

@@ -151,6 +151,9 @@ class JaumannRate(jit.JitLaw):
     def _refuse(what: str):
         raise NotImplementedError(f"JaumannRate: {what} is not supported for objective-rate wrappers")
 
+    def evaluate_path(self, *args, **kwargs):
+        self._refuse("evaluate_path (a Mandel load path has no spin)")
+
     # -- interface ------------------------------------------------------------------------------------------------------
     @property
     def constraint(self) -> StressStrainConstraint:

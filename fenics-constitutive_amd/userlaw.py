@@ -18,7 +18,12 @@ A parameter given in ``fields`` instead of ``parameters`` is a per-point field: 
 point's lane (``csrc/jit/user_law_fields.h``).  The source does not change: a field is a ``double`` member of ``UserParams`` like a
 scalar.
 
-FULL constraint, ``evaluate`` / ``evaluate_from``: the resident, batched, indexed and multi-GPU forms of the built-in laws are
+``evaluate_path`` drives every point through a whole load path of S increments in one launch, with the state in registers
+across the steps and any set of Mandel components stress-controlled (a Newton loop per point on the law's own tangent entries,
+or on ``Dual`` partials seeded on the controlled components only): the kernel template ``csrc/jit/user_law_path.hip``, compiled
+on first use per control set behind the same generated definitions.  Implicit laws: strain control only.
+
+FULL constraint, ``evaluate`` / ``evaluate_from`` / ``evaluate_path``: the resident, batched, indexed and multi-GPU forms of the built-in laws are
 refused with ``NotImplementedError``.
 """
 
@@ -30,8 +35,8 @@ import warnings
 
 import numpy as np
 
-from . import jit
-from .device import _check_torch, _is_torch
+from . import _capi, jit
+from .device import _check_numpy, _check_torch, _is_torch, _size
 from .interfaces import StressStrainConstraint
 from .jit import UserLawCompileError, _cache, compile_count  # noqa: F401 (importable from here, as before jit.py)
 
@@ -46,6 +51,12 @@ WAVES_PER_SIMD = (4, 3, 2)
 #: as 8-byte entries (SpringMaxwellModel: 2.09x the time of K = 6 at 3 instead of 2 waves); then the most waves
 #: with the fewest passes
 AD_LADDER = tuple((w, 6) for w in WAVES_PER_SIMD) + tuple((w, k) for w in WAVES_PER_SIMD for k in (3, 2, 1))
+#: the path kernel (evaluate_path) holds the committed and the trial state, the load row and the control system next to the
+#: law's temporaries: its ladder goes down to a lone wave per SIMD (512 registers), as IMPLICIT_BUDGETS does
+PATH_WAVES_PER_SIMD = (4, 3, 2, 1)
+PATH_KERNEL = "fcamd_user_law_path_kernel"
+#: evaluate_path: max_iter and tol of the stress-control Newton loop
+PATH_NEWTON_DEFAULTS = {"max_iter": 25, "tol": 1e-10}
 TANGENT_MODES = ("explicit", "autodiff", "implicit")
 #: implicit laws: the most local unknowns (an 8 x 8 Jacobian and its right-hand sides stay in registers)
 MAX_UNKNOWNS = 8
@@ -153,13 +164,52 @@ def implicit_ladder(unknowns: int, tangent: bool, state_doubles: int = 6) -> tup
     return fit or rungs[-1:]
 
 
-def _newton_options(newton) -> dict:
+def _control_set(stress_controlled) -> tuple:
+    """evaluate_path's ``stress_controlled`` as a tuple of distinct Mandel component indices 0-5"""
+    if isinstance(stress_controlled, (str, bytes)) or not hasattr(stress_controlled, "__iter__"):
+        raise ValueError(f"UserLaw: stress_controlled={stress_controlled!r}; expected a tuple of component indices 0-5")
+    out = []
+    for c in stress_controlled:
+        if isinstance(c, bool) or not hasattr(c, "__index__"):
+            raise ValueError(f"UserLaw: stress_controlled holds {c!r}; expected ints (Mandel component indices 0-5)")
+        c = c.__index__()
+        if not 0 <= c <= 5:
+            raise ValueError(f"UserLaw: stress_controlled holds {c}; Mandel component indices are 0-5")
+        if c in out:
+            raise ValueError(f"UserLaw: stress_controlled holds {c} more than once")
+        out.append(c)
+    return tuple(out)
+
+
+def _path_del_t(del_t):
+    """evaluate_path's time increments, float64 [S]: (S, the contiguous ROCm tensor that holds them or None, the host array or None)"""
+    if _is_torch(del_t):
+        import torch
+
+        if del_t.dtype != torch.float64:
+            raise TypeError(f"del_t must be float64, got {del_t.dtype}")
+        if del_t.dim() != 1:
+            raise ValueError(f"del_t must be 1-D (one increment per step), got shape {tuple(del_t.shape)}")
+        if del_t.is_cuda and del_t.is_contiguous():
+            return int(del_t.shape[0]), del_t, None
+        del_t = del_t.detach().cpu().contiguous().numpy()
+    if not isinstance(del_t, np.ndarray):
+        raise TypeError(f"del_t must be a 1-D float64 array of time increments, got {type(del_t).__name__}")
+    if del_t.dtype != np.float64:
+        raise TypeError(f"del_t must be float64, got {del_t.dtype}")
+    if del_t.ndim != 1:
+        raise ValueError(f"del_t must be 1-D (one increment per step), got shape {del_t.shape}")
+    return len(del_t), None, np.ascontiguousarray(del_t)
+
+
+def _newton_options(newton, defaults=None) -> dict:
+    defaults = NEWTON_DEFAULTS if defaults is None else defaults
     if newton is None:
-        return dict(NEWTON_DEFAULTS)
+        return dict(defaults)
     if not hasattr(newton, "items"):
-        raise ValueError(f"UserLaw: newton must be a dict with the keys {sorted(NEWTON_DEFAULTS)}, not {newton!r}")
-    if set(newton) != set(NEWTON_DEFAULTS):
-        raise ValueError(f"UserLaw: newton has the keys {sorted(map(str, newton))}; expected exactly {sorted(NEWTON_DEFAULTS)}")
+        raise ValueError(f"UserLaw: newton must be a dict with the keys {sorted(defaults)}, not {newton!r}")
+    if set(newton) != set(defaults):
+        raise ValueError(f"UserLaw: newton has the keys {sorted(map(str, newton))}; expected exactly {sorted(defaults)}")
     max_iter, tol = newton["max_iter"], newton["tol"]
     if isinstance(max_iter, bool) or not hasattr(max_iter, "__index__") or not 0 <= max_iter.__index__() < 2 ** 31:
         raise ValueError(f"UserLaw: newton['max_iter'] = {max_iter!r}; expected an int >= 0")
@@ -287,20 +337,28 @@ class UserLaw(jit.JitLaw):
         self._counters = {}  # device -> int64 device word (non-converged points of the last launch)
         self._empty = {}  # device -> the last call had no points
         self._args_cls = _args_type(max(1, len(self._hist)), len(self._field_names))
+        self._path_compiled = {}  # stress-controlled components -> (code object, rung) of the path kernel, compiled on first use
+        self._path_args_cls = _path_args_type(max(1, len(self._hist)), len(self._field_names))
 
     # -- program --------------------------------------------------------------------------------------------------------
-    def _program(self, source: str, waves: int, directions: int = None, implicit: tuple = None) -> str:
+    def _program(self, source: str, waves: int, directions: int = None, implicit: tuple = None, path: tuple = None) -> str:
         """the generated definitions, the user's source, the kernel template.  ``directions``: autodiff mode's partials per
         Dual (0: the stress-only kernel); None in explicit mode.  ``implicit``: implicit mode's (directions per Jacobian pass,
-        directions per tangent pass; 0: the stress-only kernel)"""
+        directions per tangent pass; 0: the stress-only kernel).  ``path``: the stress-controlled components of the path kernel
+        (``evaluate_path``, csrc/jit/user_law_path.hip); None: an evaluate kernel"""
         ad = directions is not None or implicit is not None
         template = "user_law_implicit.hip" if implicit is not None else "user_law_ad.hip" if ad else "user_law.hip"
+        if path is not None:
+            template = "user_law_path.hip"
         p, f = self._param_names, self._field_names
         history, scalar = ("template <class T> struct UserHistoryT {", "T") if ad else ("struct UserHistory {", "double")
         mode = [f"#define FCAMD_USER_AD_K {directions}"] if directions is not None else []
         if implicit is not None:
             mode = [f"#define FCAMD_USER_UNKNOWNS {self._unknowns}", f"#define FCAMD_USER_IM_KJ {implicit[0]}",
                     f"#define FCAMD_USER_IM_KT {implicit[1]}", f"#define FCAMD_USER_IM_SLOT {len(p)}"]
+        if path is not None:
+            mode += [f"#define FCAMD_USER_PATH {3 if implicit is not None else 2 if ad else 1}", f"#define FCAMD_PATH_NCTRL {len(path)}"]
+            mode += ["#define FCAMD_PATH_CTRL " + ", ".join(map(str, path))] if path else []
         lines = ['#include "user_law_implicit.h"' if implicit is not None else '#include "user_law_ad.h"' if ad else '#include "user_law_api.h"',
                  f"#define FCAMD_USER_WAVES {waves}",
                  *mode,
@@ -332,6 +390,12 @@ class UserLaw(jit.JitLaw):
     def _program_implicit(self, source: str, waves: int, jacobian_directions: int, tangent_directions: int) -> str:
         """the program of implicit mode (``tangent_directions``: 0 for the stress-only kernel)"""
         return self._program(source, waves, implicit=(jacobian_directions, tangent_directions))
+
+    def _program_path(self, source: str, waves: int, stress_controlled: tuple, jacobian_directions: int = None) -> str:
+        """the program of the path kernel (``jacobian_directions``: implicit mode's, as in its stress-only kernel)"""
+        if self.tangent_mode == "implicit":
+            return self._program(source, waves, implicit=(jacobian_directions, 0), path=stress_controlled)
+        return self._program(source, waves, 0 if self.tangent_mode == "autodiff" else None, path=stress_controlled)
 
     @property
     def unknowns(self):
@@ -499,6 +563,164 @@ class UserLaw(jit.JitLaw):
         blocks = min(((n + 63) // 64 + 3) // 4, 512 * jit.num_cu(dev))  # a wave per 64-point tile, 4 waves per block
         jit.launch(self._compiled if tangent is not None else self._compiled_stress, dev, blocks, a, f"UserLaw '{self.name}' launch")
 
+    # -- evaluate_path ----------------------------------------------------------------------------------------------------
+    def _path_kernel(self, stress_controlled: tuple):
+        """(code object, rung) of the path kernel for the control set, compiled on first use: the first rung of its ladder
+        without scratch (explicit and autodiff laws: ``PATH_WAVES_PER_SIMD``; implicit laws: ``implicit_ladder``'s stress-only
+        rungs)"""
+        hit = self._path_compiled.get(stress_controlled)
+        if hit is not None:
+            return hit
+        if self._rotate is not None:
+            self._refuse("evaluate_path with an objective rate (a Mandel load path has no spin)")
+        if self.tangent_mode == "implicit":
+            if stress_controlled:
+                raise NotImplementedError(f"UserLaw '{self.name}': evaluate_path with stress_controlled={stress_controlled} on an implicit "
+                                          "law: implicit laws are driven under strain control only (their in-register tangent is "
+                                          "not formed by the path kernel); use the law's explicit or autodiff form")
+            rungs = implicit_ladder(self._unknowns, False, 2 * (6 + sum(d for _, d in self._hist)))
+        else:
+            rungs = tuple((w,) for w in PATH_WAVES_PER_SIMD)
+        for rung in rungs:
+            code = jit.compile_program(self._program_path(self.source, rung[0], stress_controlled, *rung[1:]), self.name, PATH_KERNEL)
+            if not code.resources.get("scratch_bytes"):
+                break
+        if code.resources.get("scratch_bytes"):
+            warnings.warn(f"UserLaw '{self.name}': the path kernel uses {code.resources['scratch_bytes']} bytes of scratch per lane "
+                          f"(VGPRs: {code.resources.get('vgprs')}); register spills cost memory bandwidth", UserWarning, stacklevel=3)
+        hit = self._path_compiled[stress_controlled] = (code, rung)
+        return hit
+
+    def path_resources(self, stress_controlled=()) -> dict:
+        """``resources`` of the path kernel for ``stress_controlled`` (compiled on first use; no GPU needed), with
+        ``"rung_waves_per_simd"``, the budget the kernel was cut for"""
+        code, rung = self._path_kernel(_control_set(stress_controlled))
+        r = dict(code.resources, rung_waves_per_simd=rung[0])
+        if len(rung) > 1:
+            r["jacobian_directions_per_pass"] = rung[1]
+        return r
+
+    def evaluate_path(self, t0, del_t, load, stress, history, *, stress_controlled=(), stress_path=None, strain_path=None,
+                      newton=None, check: bool = False):
+        """Drive every point through a load path of ``S = len(del_t)`` increments in one launch; returns the int32 array (or
+        tensor) ``[n]`` of the first step each point failed, -1 for a point that completed.
+
+        ``del_t``: float64 ``[S]`` (an ndarray, or a ROCm tensor, which is used where it lies); step k runs at ``t_k``
+        (``t_0 = t0``, ``t_{k+1} = t_k + del_t[k]``, summed in this order in double) with ``del_t[k]``.
+        ``load``: float64 ``[S, 6]`` (one path for all points) or ``[S, n, 6]``, Mandel components: the strain increment of the step for a component not in ``stress_controlled``, the total stress the step must reach for one
+        in it.  ``stress_controlled``: distinct component indices 0-5, the same for all steps and points.  ``stress`` ``[6 n]`` and
+        ``history``: the committed state, updated in place to the state after the last step a point completed.
+
+        ``stress_path``, ``strain_path``: optional float64 ``[S, n, 6]`` records, step-major: the stress after each step and the
+        Mandel strain increment each step applied (prescribed and solved components).  A point fails at a step when the point
+        function returns non-zero at the step's last evaluation or the control Newton loop (``newton``: ``{"max_iter", "tol"}``,
+        default 25 and 1e-10; converged when ``max_c |sigma_c - target_c| <= tol``) does not converge: it keeps its committed
+        state, its records are NaN from that step on and it takes no further part.  ``check=True`` synchronises and raises the
+        reference's non-convergence ``RuntimeError`` if a point failed, after everything is written.
+
+        Device tensors: asynchronous on torch's current stream.  NumPy arrays: staged through device copies, synchronous.
+        Implicit laws: strain control only (``NotImplementedError`` otherwise).  The algorithm: DESIGN.md §17."""
+        self._refuse_batched()
+        if self._rotate is not None:
+            self._refuse("evaluate_path with an objective rate (a Mandel load path has no spin)")
+        ctrl = _control_set(stress_controlled)
+        opts = _newton_options(newton, PATH_NEWTON_DEFAULTS)
+        hist = self._history_arrays(history)
+        S, dts_dev, dts = _path_del_t(del_t)
+        if _size(stress) % 6:
+            raise ValueError(f"stress has {_size(stress)} entries, not a multiple of 6")
+        n = _size(stress) // 6
+        for (name, dim), h in zip(self._hist, hist):
+            assert _size(h) == n * dim, f"history '{name}' has the wrong length"
+        shape = tuple(load.shape) if hasattr(load, "shape") else None
+        if shape not in ((S, 6), (S, n, 6)):
+            raise ValueError(f"load has shape {shape}; expected ({S}, 6) (one path for all points) or ({S}, {n}, 6)")
+        per_point = len(shape) == 3
+        for label, rec in (("stress_path", stress_path), ("strain_path", strain_path)):
+            if rec is not None and _size(rec) != S * n * 6:
+                raise ValueError(f"{label} has {_size(rec)} entries; expected {S} x {n} x 6")
+        self._check_field_points(n)
+        arrays = [("load", load), ("stress", stress)] + [(f"history['{n_}']", h) for (n_, _), h in zip(self._hist, hist)]
+        arrays += [(label, rec) for label, rec in (("stress_path", stress_path), ("strain_path", strain_path)) if rec is not None]
+        code, _ = self._path_kernel(ctrl)  # an implicit law under stress control is refused here, before any device work
+        t0 = float(t0)
+        from .hostio import download, to_device, to_host
+
+        if _is_torch(stress):
+            dev = stress.device.index or 0
+            if dts_dev is not None and (dts_dev.device.index or 0) != dev:
+                raise ValueError(f"del_t is on {dts_dev.device}, stress on cuda:{dev}")
+            for label, a in arrays:
+                _check_torch(label, a)
+                if (a.device.index or 0) != dev:
+                    raise ValueError(f"{label} is on {a.device}, stress on cuda:{dev}")
+                if a.data_ptr() % 16:
+                    raise ValueError(f"{label}: device arrays must be 16-byte aligned")
+            if dts_dev is None and S and n:
+                import torch
+
+                # a small pageable copy on torch's current stream (above 1 MiB: hostio's page-locked one, which waits for the stream)
+                dts_dev = torch.from_numpy(dts).to(stress.device) if dts.nbytes < (1 << 20) else to_device(dts, stress.device)
+            failed = self._path_device(code, dev, t0, S, dts_dev, n, per_point, load, stress, hist, stress_path, strain_path, opts)
+            if check:
+                self._raise(int((failed >= 0).sum().item()))
+            return failed
+        import torch
+
+        for label, a in arrays:
+            _check_numpy(label, a)
+        if S == 0 or n == 0:
+            return np.full(n, -1, dtype=np.int32)
+        dev = _capi.default_device()
+        d = torch.device("cuda", dev)
+        with torch.cuda.device(d):
+            s = to_device(stress.reshape(-1), d)
+            hd = [to_device(h.reshape(-1), d) for h in hist]
+            recs = [None if r is None else torch.empty(S * n * 6, dtype=torch.float64, device=d) for r in (stress_path, strain_path)]
+            if dts_dev is None or (dts_dev.device.index or 0) != dev:
+                dts_dev = to_device(to_host(dts_dev) if dts is None else dts, d)
+            failed = self._path_device(code, dev, t0, S, dts_dev, n, per_point, to_device(load.reshape(-1), d), s, hd, recs[0], recs[1], opts)
+            out = to_host(failed)
+            download(stress.reshape(-1), s)
+            for h, x in zip(hist, hd):
+                download(h.reshape(-1), x)
+            for r, x in zip((stress_path, strain_path), recs):
+                if r is not None:
+                    download(r.reshape(-1), x)
+        if check:
+            self._raise(int((out >= 0).sum()))
+        return out
+
+    def _path_device(self, code, dev, t0, S, del_t, n, per_point, load, stress, hist, stress_path, strain_path, opts):
+        """the launch on checked device tensors (``del_t``: the [S] tensor of the increments); returns the int32 tensor of failed
+        steps"""
+        import torch
+
+        with torch.cuda.device(dev):
+            failed = torch.full((n,), -1, dtype=torch.int32, device=torch.device("cuda", dev))
+        if S == 0 or n == 0:  # nothing is launched
+            return failed
+        a = self._path_args_cls()
+        a.load, a.del_t, a.stress = load.data_ptr(), del_t.data_ptr(), stress.data_ptr()
+        for k, h in enumerate(hist):
+            a.h[k] = h.data_ptr()
+        a.stress_path = None if stress_path is None else stress_path.data_ptr()
+        a.strain_path = None if strain_path is None else strain_path.data_ptr()
+        a.failed = failed.data_ptr()
+        a.n, a.steps, a.per_point, a.max_iter = n, S, int(per_point), opts["max_iter"]
+        a.t0, a.tol, a.factor, a.sq2 = t0, opts["tol"], FACTOR_PY, 2 ** 0.5
+        for k, v in enumerate(self._param_values):
+            a.params[k] = v
+        if self._newton is not None:  # FCAMD_USER_IM_SLOT: behind the law's own parameters
+            a.params[len(self._param_values)] = float(self._newton["max_iter"])
+            a.params[len(self._param_values) + 1] = self._newton["tol"]
+        for k, ptr in enumerate(self._field_ptrs(dev) if self._field_values else ()):
+            a.fields[k] = ptr
+        blocks = min(((n + 63) // 64 + 3) // 4, 512 * jit.num_cu(dev))  # a wave per 64-point tile, 4 waves per block
+        jit.launch(code, dev, blocks, a, f"UserLaw '{self.name}' path launch")
+        del_t.record_stream(torch.cuda.current_stream(dev))  # a copy made for this call is freed at return; the launch reads it
+        return failed
+
     def device_stats(self, device: int = 0) -> int:
         """Synchronise with the last launch on ``device`` and return its number of non-converged points (does not raise)."""
         c = self._counters.get(device)
@@ -519,3 +741,16 @@ def _args_type(nh: int, nf: int = 0):
                     ("params", C.c_double * MAX_PARAMS)] + ([("fields", vp * nf)] if nf else [])
 
     return UserArgs
+
+
+def _path_args_type(nh: int, nf: int = 0):
+    """ctypes mirror of PathArgs (user_law_path.hip) for ``nh`` history slots and ``nf`` parameter fields (behind the other members)"""
+    vp = C.c_void_p
+
+    class PathArgs(C.Structure):
+        _fields_ = [("load", vp), ("del_t", vp), ("stress", vp), ("h", vp * nh), ("stress_path", vp), ("strain_path", vp),
+                    ("failed", vp), ("n", C.c_int64), ("steps", C.c_int64), ("per_point", C.c_int64), ("max_iter", C.c_int64),
+                    ("t0", C.c_double), ("tol", C.c_double), ("factor", C.c_double), ("sq2", C.c_double), ("params", C.c_double * MAX_PARAMS)] \
+            + ([("fields", vp * nf)] if nf else [])
+
+    return PathArgs
