@@ -150,7 +150,7 @@ __device__ __forceinline__ unsigned long long user_tile(const UserArgs& a, const
 
 }  // namespace fcamd_user
 
-#ifndef FCAMD_USER_PATH  // user_law_path.hip has a kernel of its own around the helpers above
+#if !defined(FCAMD_USER_PATH) && !defined(FCAMD_USER_WRAP)  // user_law_path.hip and user_law_wrapped.hip have kernels of their own around the helpers above
 // FCAMD_USER_WAVES (generated): waves per SIMD the register budget is cut for -- 4 (128 VGPRs, what the LDS allows), or fewer
 // for a law that spills at 4 (userlaw.py recompiles it)
 extern "C" __global__ void __launch_bounds__(fcamd::kBlock, FCAMD_USER_WAVES) fcamd_user_law_kernel(const fcamd_user::UserArgs a) {
@@ -180,4 +180,4 @@ extern "C" __global__ void __launch_bounds__(fcamd::kBlock, FCAMD_USER_WAVES) fc
 #endif
     if (bad != 0 && lane == 0) atomicAdd(a.nonconv, bad);
 }
-#endif  // FCAMD_USER_PATH
+#endif  // FCAMD_USER_PATH, FCAMD_USER_WRAP

@@ -23,6 +23,12 @@ across the steps and any set of Mandel components stress-controlled (a Newton lo
 or on ``Dual`` partials seeded on the controlled components only): the kernel template ``csrc/jit/user_law_path.hip``, compiled
 on first use per control set behind the same generated definitions.  Implicit laws: strain control only.
 
+The 1-D / 2-D wrappers (``wrappers.py``: uniaxial strain, plane strain, plane stress, uniaxial stress) run a law with an explicit
+or autodiff tangent as one launch of the kernel template ``csrc/jit/user_law_wrapped.hip``, compiled on first use per wrapper
+(``_wrapped_kernel``, ``wrapped_resources``; the launch: ``_evaluate_wrapped``): map, evaluate -- under the stress wrappers inside a
+Newton loop per point in registers -- and map back, with only the wrapper's cached 3-D stress next to the low-dimensional arrays
+(DESIGN.md §18).  Implicit laws go through the wrappers' generic path.
+
 FULL constraint, ``evaluate`` / ``evaluate_from`` / ``evaluate_path``: the resident, batched, indexed and multi-GPU forms of the built-in laws are
 refused with ``NotImplementedError``.
 """
@@ -57,6 +63,13 @@ PATH_WAVES_PER_SIMD = (4, 3, 2, 1)
 PATH_KERNEL = "fcamd_user_law_path_kernel"
 #: evaluate_path: max_iter and tol of the stress-control Newton loop
 PATH_NEWTON_DEFAULTS = {"max_iter": 25, "tol": 1e-10}
+#: the 1-D / 2-D wrappers (wrappers.py) around an explicit or autodiff law: one kernel per wrap mode (csrc/jit/user_law_wrapped.hip),
+#: the stress wrappers with the committed and the trial state and the local Newton iteration in registers -- the path kernel's ladder
+WRAPPED_WAVES_PER_SIMD = (4, 3, 2, 1)
+WRAPPED_KERNEL = "fcamd_user_law_wrapped_kernel"
+#: FCAMD_USER_WRAP, the built-in kernels' numbering (kernels/wrapped_io.h, stress_wrapped.h)
+WRAP_MODES = {StressStrainConstraint.UNIAXIAL_STRAIN: 1, StressStrainConstraint.PLANE_STRAIN: 2,
+              StressStrainConstraint.PLANE_STRESS: 3, StressStrainConstraint.UNIAXIAL_STRESS: 4}
 TANGENT_MODES = ("explicit", "autodiff", "implicit")
 #: implicit laws: the most local unknowns (an 8 x 8 Jacobian and its right-hand sides stay in registers)
 MAX_UNKNOWNS = 8
@@ -339,17 +352,23 @@ class UserLaw(jit.JitLaw):
         self._args_cls = _args_type(max(1, len(self._hist)), len(self._field_names))
         self._path_compiled = {}  # stress-controlled components -> (code object, rung) of the path kernel, compiled on first use
         self._path_args_cls = _path_args_type(max(1, len(self._hist)), len(self._field_names))
+        self._wrapped_compiled = {}  # wrap mode -> (code object, rung) of the wrapped kernel, compiled on first use
+        self._wrapped_args_cls = _wrapped_args_type(max(1, len(self._hist)))
 
     # -- program --------------------------------------------------------------------------------------------------------
-    def _program(self, source: str, waves: int, directions: int = None, implicit: tuple = None, path: tuple = None) -> str:
+    def _program(self, source: str, waves: int, directions: int = None, implicit: tuple = None, path: tuple = None,
+                 wrap: int = None) -> str:
         """the generated definitions, the user's source, the kernel template.  ``directions``: autodiff mode's partials per
         Dual (0: the stress-only kernel); None in explicit mode.  ``implicit``: implicit mode's (directions per Jacobian pass,
         directions per tangent pass; 0: the stress-only kernel).  ``path``: the stress-controlled components of the path kernel
-        (``evaluate_path``, csrc/jit/user_law_path.hip); None: an evaluate kernel"""
+        (``evaluate_path``, csrc/jit/user_law_path.hip); None: an evaluate kernel.  ``wrap``: the wrap mode of the wrapped kernel
+        (the 1-D / 2-D wrappers, csrc/jit/user_law_wrapped.hip)"""
         ad = directions is not None or implicit is not None
         template = "user_law_implicit.hip" if implicit is not None else "user_law_ad.hip" if ad else "user_law.hip"
         if path is not None:
             template = "user_law_path.hip"
+        if wrap is not None:
+            template = "user_law_wrapped.hip"
         p, f = self._param_names, self._field_names
         history, scalar = ("template <class T> struct UserHistoryT {", "T") if ad else ("struct UserHistory {", "double")
         mode = [f"#define FCAMD_USER_AD_K {directions}"] if directions is not None else []
@@ -359,6 +378,8 @@ class UserLaw(jit.JitLaw):
         if path is not None:
             mode += [f"#define FCAMD_USER_PATH {3 if implicit is not None else 2 if ad else 1}", f"#define FCAMD_PATH_NCTRL {len(path)}"]
             mode += ["#define FCAMD_PATH_CTRL " + ", ".join(map(str, path))] if path else []
+        if wrap is not None:
+            mode += [f"#define FCAMD_USER_WRAP {wrap}"]
         lines = ['#include "user_law_implicit.h"' if implicit is not None else '#include "user_law_ad.h"' if ad else '#include "user_law_api.h"',
                  f"#define FCAMD_USER_WAVES {waves}",
                  *mode,
@@ -396,6 +417,10 @@ class UserLaw(jit.JitLaw):
         if self.tangent_mode == "implicit":
             return self._program(source, waves, implicit=(jacobian_directions, 0), path=stress_controlled)
         return self._program(source, waves, 0 if self.tangent_mode == "autodiff" else None, path=stress_controlled)
+
+    def _program_wrapped(self, source: str, waves: int, wrap: int) -> str:
+        """the program of the wrapped kernel (``wrap``: 1 uniaxial strain, 2 plane strain, 3 plane stress, 4 uniaxial stress)"""
+        return self._program(source, waves, 0 if self.tangent_mode == "autodiff" else None, wrap=wrap)
 
     @property
     def unknowns(self):
@@ -721,6 +746,91 @@ class UserLaw(jit.JitLaw):
         del_t.record_stream(torch.cuda.current_stream(dev))  # a copy made for this call is freed at return; the launch reads it
         return failed
 
+    # -- the 1-D / 2-D wrappers ---------------------------------------------------------------------------------------------
+    def _wrapped_kernel(self, wrap: int):
+        """(code object, rung) of the wrapped kernel for the wrap mode (1 uniaxial strain, 2 plane strain, 3 plane stress,
+        4 uniaxial stress), compiled on first use: the first rung of ``WRAPPED_WAVES_PER_SIMD`` without scratch"""
+        hit = self._wrapped_compiled.get(wrap)
+        if hit is not None:
+            return hit
+        if wrap not in WRAP_MODES.values():
+            raise ValueError(f"UserLaw: wrap mode {wrap!r}; expected one of {sorted(WRAP_MODES.values())}")
+        if self.tangent_mode == "implicit":
+            raise NotImplementedError(f"UserLaw '{self.name}': implicit laws have no fused wrapper kernel (their in-register tangent "
+                                      "is a pass structure, not a function that returns partials); the wrappers take the generic path")
+        if self._rotate is not None:
+            self._refuse("the 1-D / 2-D wrappers with an objective rate")
+        if self._field_names:
+            self._refuse("the 1-D / 2-D wrappers with per-point parameter fields")
+        for waves in WRAPPED_WAVES_PER_SIMD:
+            code = jit.compile_program(self._program_wrapped(self.source, waves, wrap), self.name, WRAPPED_KERNEL)
+            if not code.resources.get("scratch_bytes"):
+                break
+        if code.resources.get("scratch_bytes"):
+            warnings.warn(f"UserLaw '{self.name}': the wrapped kernel (mode {wrap}) uses {code.resources['scratch_bytes']} bytes of "
+                          f"scratch per lane (VGPRs: {code.resources.get('vgprs')}); register spills cost memory bandwidth",
+                          UserWarning, stacklevel=3)
+        hit = self._wrapped_compiled[wrap] = (code, (waves,))
+        return hit
+
+    def wrapped_resources(self, constraint) -> dict:
+        """``resources`` of the kernel that runs this law under the wrapper of ``constraint`` (UNIAXIAL_STRAIN, PLANE_STRAIN,
+        PLANE_STRESS or UNIAXIAL_STRESS; compiled on first use; no GPU needed), with ``"rung_waves_per_simd"``, the budget the
+        kernel was cut for.  Implicit laws: ``NotImplementedError`` (the wrappers run them through the generic path)."""
+        if constraint not in WRAP_MODES:
+            raise ValueError(f"UserLaw: wrapped_resources({constraint!r}); expected one of {[c.name for c in WRAP_MODES]}")
+        code, rung = self._wrapped_kernel(WRAP_MODES[constraint])
+        return dict(code.resources, rung_waves_per_simd=rung[0])
+
+    def _evaluate_wrapped(self, constraint, t, del_t, grad, stress, tangent, cache3d, history) -> None:
+        """The launch of the wrappers (wrappers._From3D.evaluate) on device tensors, in place: the low-dimensional ``grad``,
+        ``stress`` and ``tangent`` of ``constraint``, the wrapper's cached 3-D stress rows ``cache3d`` ``[6 n]`` and the law's
+        history.  Asynchronous on torch's current stream; ``device_stats`` returns the number of failed points.  Everything is
+        validated before anything is launched."""
+        self._refuse_batched()
+        if constraint not in WRAP_MODES:
+            raise ValueError(f"UserLaw: constraint {constraint!r} has no wrapper; expected one of {[c.name for c in WRAP_MODES]}")
+        wrap = WRAP_MODES[constraint]
+        gd2, sd = constraint.geometric_dim ** 2, constraint.stress_strain_dim
+        hist = self._history_arrays(history)
+        arrays = [("grad_del_u", grad), ("stress", stress), ("tangent", tangent), ("stress_3d", cache3d)]
+        arrays += [(f"history['{n_}']", h) for (n_, _), h in zip(self._hist, hist)]
+        for label, a in arrays:
+            _check_torch(label, a)
+        dev = grad.device.index or 0
+        for label, a in arrays:
+            if (a.device.index or 0) != dev:
+                raise ValueError(f"{label} is on {a.device}, grad_del_u on cuda:{dev}")
+            if a.data_ptr() % 16:
+                raise ValueError(f"{label}: device arrays must be 16-byte aligned")
+        if _size(grad) % gd2:
+            raise ValueError(f"grad_del_u has {_size(grad)} entries, not a multiple of {gd2} ({constraint.name})")
+        n = _size(grad) // gd2
+        if _size(stress) != sd * n or _size(tangent) != sd * sd * n:
+            raise ValueError(f"{constraint.name} over {n} points: stress has {_size(stress)} entries (expected {sd * n}), tangent "
+                             f"{_size(tangent)} (expected {sd * sd * n})")
+        if _size(cache3d) != 6 * n:
+            raise ValueError(f"stress_3d has {_size(cache3d)} entries; the cached 3-D stress of {n} points has {6 * n}")
+        for (name, dim), h in zip(self._hist, hist):
+            if _size(h) != n * dim:
+                raise ValueError(f"history '{name}' has {_size(h)} entries; expected {n} x {dim}")
+        code, _ = self._wrapped_kernel(wrap)  # an implicit law is refused here
+        self._empty[dev] = n == 0
+        if n == 0:  # nothing is launched (device_stats: 0)
+            return
+        counter = self._counter(dev)
+        counter.zero_()  # on torch's current stream: the launch's stream
+        a = self._wrapped_args_cls()
+        a.grad, a.stress, a.tangent, a.cache3d = grad.data_ptr(), stress.data_ptr(), tangent.data_ptr(), cache3d.data_ptr()
+        for k, h in enumerate(hist):
+            a.h[k] = h.data_ptr()
+        a.nonconv = counter.data_ptr()
+        a.n, a.t, a.del_t, a.factor = n, float(t), float(del_t), FACTOR_PY
+        for k, v in enumerate(self._param_values):
+            a.params[k] = v
+        blocks = min(((n + 63) // 64 + 3) // 4, 512 * jit.num_cu(dev))  # a wave per 64-point tile, 4 waves per block
+        jit.launch(code, dev, blocks, a, f"UserLaw '{self.name}' wrapped launch ({constraint.name})")
+
     def device_stats(self, device: int = 0) -> int:
         """Synchronise with the last launch on ``device`` and return its number of non-converged points (does not raise)."""
         c = self._counters.get(device)
@@ -754,3 +864,14 @@ def _path_args_type(nh: int, nf: int = 0):
             + ([("fields", vp * nf)] if nf else [])
 
     return PathArgs
+
+
+def _wrapped_args_type(nh: int):
+    """ctypes mirror of WrappedArgs (user_law_wrapped.hip) for ``nh`` history slots"""
+    vp = C.c_void_p
+
+    class WrappedArgs(C.Structure):
+        _fields_ = [("grad", vp), ("stress", vp), ("tangent", vp), ("cache3d", vp), ("h", vp * nh), ("nonconv", vp), ("n", C.c_int64),
+                    ("t", C.c_double), ("del_t", C.c_double), ("factor", C.c_double), ("params", C.c_double * MAX_PARAMS)]
+
+    return WrappedArgs

@@ -18,6 +18,11 @@ call like the reference's in-place arrays).
 out-of-plane strain increments that make the constrained stresses vanish: a local Newton iteration around the
 3-D law ("The f3 stress wrappers"), fused into one kernel for the same laws, and an array-level Newton
 iteration around the 3-D model's own ``evaluate`` otherwise.
+
+Around a ``UserLaw`` with an explicit or autodiff tangent all four wrappers are one launch of a kernel compiled at run time
+from the law's own point function (``csrc/jit/user_law_wrapped.hip``): the strain wrappers compute the bits of
+map -> evaluate -> map, the stress wrappers run the local Newton iteration per point in registers from a zero increment.
+Implicit user laws take the generic path.
 """
 
 from __future__ import annotations
@@ -33,10 +38,18 @@ from .interfaces import IncrSmallStrainModel, StressStrainConstraint
 __all__ = ["UniaxialStrainFrom3D", "PlaneStrainFrom3D", "UniaxialStressFrom3D", "PlaneStressFrom3D"]
 
 
+def _has_wrapped_kernel(model) -> bool:
+    """the law is a UserLaw the wrappers run as one kernel: explicit or autodiff tangent (implicit laws keep the generic path)"""
+    from .userlaw import UserLaw
+
+    return isinstance(model, UserLaw) and model.tangent_mode in ("explicit", "autodiff") and model._rotate is None
+
+
 class _From3D(IncrSmallStrainModel):
     _constraint: StressStrainConstraint
     _kinds: tuple[int, int, int, int]  # grad->3d, stress->3d, stress<-3d, tangent<-3d
-    #: use the fused kernel where one exists (LinearElasticityModel, the plasticity laws); False forces map -> evaluate -> map
+    #: use the fused kernel where one exists (LinearElasticityModel, the plasticity laws, user laws with an explicit or autodiff
+    #: tangent); False forces map -> evaluate -> map
     fused = True
 
     def __init__(self, model: IncrSmallStrainModel) -> None:
@@ -103,6 +116,17 @@ class _From3D(IncrSmallStrainModel):
             if host:
                 self.model.device_stats(dev.index or 0)  # raises on Newton non-convergence like the reference
                 self._download(stress, tangent, history, s_lo, t_lo, h_dev)
+            return
+        if self.fused and _has_wrapped_kernel(self.model):
+            # a user law with an explicit or autodiff tangent: its own fused kernel (csrc/jit/user_law_wrapped.hip), compiled on
+            # first use per wrapper; only the cached 3-D stress exists.  Tensors: asynchronous, the count of failed points in
+            # model.device_stats(); ndarrays: the results are downloaded, then the reference's RuntimeError is raised
+            if self.stress_3d is None or self.stress_3d.numel() != 6 * n or self.stress_3d.device != dev:
+                self.stress_3d = torch.zeros(6 * n, dtype=torch.float64, device=dev)
+            self.model._evaluate_wrapped(self._constraint, t, del_t, g_lo, s_lo, t_lo, self.stress_3d, h_dev)
+            if host:
+                self._download(stress, tangent, history, s_lo, t_lo, h_dev)
+                self.model._raise(self.model.device_stats(dev.index or 0))
             return
         if self.grad_del_u_3d is None or self.grad_del_u_3d.numel() != 9 * n or self.grad_del_u_3d.device != dev:
             # cached 3-D arrays (utils.py:253-266): zero-initialised once, unmapped components persist
