@@ -22,6 +22,7 @@ from .models import (  # noqa: F401
 )
 from .userlaw import UserLaw, UserLawCompileError  # noqa: F401
 from .objective import JaumannRate  # noqa: F401
+from .gradient import DisplacementGradient  # noqa: F401
 from .wrappers import PlaneStrainFrom3D, PlaneStressFrom3D, UniaxialStrainFrom3D, UniaxialStressFrom3D  # noqa: F401
 from .utils import get_elastic_tangent, get_identity, lame_parameters, strain_from_grad_u  # noqa: F401
 
@@ -45,6 +46,7 @@ __all__ = [
     "UserLaw",
     "UserLawCompileError",
     "JaumannRate",
+    "DisplacementGradient",
     "lame_parameters",
     "get_elastic_tangent",
     "get_identity",

@@ -30,6 +30,7 @@ EVAL_SPARSE_TANGENT = 1
 EVAL_SPLIT_HISTORY = 4
 EVAL_PACKED_HISTORY = 8
 EVAL_PARAM_FIELDS = 16  # per-point parameters: the field table travels in fcamd_eval_args.stress_3d
+EVAL_GRAD_ON_DEVICE = 32  # fcamd_evaluate_resident only: grad_del_u is a device array, read in place
 
 # context option "last_host_mode": FCAMD_HOST_* flags (include/fcamd.h)
 HOST_ZERO_COPY_IN, HOST_ZERO_COPY_OUT, HOST_TEMP_LOCK, HOST_BOUNCE = 1, 2, 4, 8

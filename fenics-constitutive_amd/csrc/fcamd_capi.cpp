@@ -361,7 +361,9 @@ int validate_call(const fcamd_model* m, double del_t, int64_t n, const void* gra
 
 // (both entries have run validate_call: the history tables of a law with history are there)
 int check_protocol(const fcamd_model* m, int64_t n, const fcamd_eval_args* x) {
-    if (x->flags & ~(FCAMD_EVAL_SPARSE_TANGENT | FCAMD_EVAL_SPLIT_HISTORY | FCAMD_EVAL_PACKED_HISTORY | FCAMD_EVAL_PARAM_FIELDS))
+    // (FCAMD_EVAL_GRAD_ON_DEVICE passes here for fcamd_evaluate_resident; the device entries have refused it: check_device_ex)
+    if (x->flags & ~(FCAMD_EVAL_SPARSE_TANGENT | FCAMD_EVAL_SPLIT_HISTORY | FCAMD_EVAL_PACKED_HISTORY | FCAMD_EVAL_PARAM_FIELDS |
+                     FCAMD_EVAL_GRAD_ON_DEVICE))
         return fail(FCAMD_ERR_UNSUPPORTED, "unknown FCAMD_EVAL_* flag in 0x%x (2, FCAMD_EVAL_DELTA_HISTORY of ABI 0.3, was removed in 0.4)", x->flags);
     if (x->history_mask && !has_sparse_history(m->law))
         return fail(FCAMD_ERR_UNSUPPORTED, "sparse trial history exists for the plasticity laws only");
@@ -843,6 +845,8 @@ static int check_device_ex(fcamd_model* m, double del_t, int64_t n, const fcamd_
                            reinterpret_cast<const void* const*>(x->history_prev),
                            reinterpret_cast<const void* const*>(x->history), x->n_hist, x->flags);
     if (st != FCAMD_OK) return st;
+    if (x->flags & FCAMD_EVAL_GRAD_ON_DEVICE)
+        return fail(FCAMD_ERR_UNSUPPORTED, "FCAMD_EVAL_GRAD_ON_DEVICE is a flag of fcamd_evaluate_resident: the gradient of a device entry is a device array already");
     // the device entries' own: the indexed form, fields, a device tangent under the sparse protocol
     if (x->parent_rows && m->constraint != FCAMD_FULL)
         return fail(FCAMD_ERR_UNSUPPORTED, "the indexed form exists for StressStrainConstraint.FULL only");

@@ -809,16 +809,20 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
     if (!x) return fail(FCAMD_ERR_BAD_ARG, "state is NULL");
     if (x->parent_rows || x->stress2 || x->tangent || x->wrapper_constraint)
         return fail(FCAMD_ERR_UNSUPPORTED, "fcamd_evaluate_resident: parent_rows / stress2 / a device tangent / the wrapper form are options of fcamd_evaluate_device_ex");
-    const double* grad = x->grad_del_u;  // HOST array
-    const int flags = x->flags;
+    // HOST array; with FCAMD_EVAL_GRAD_ON_DEVICE a DEVICE array that every launch reads in place: never looked up, locked or copied
+    const double* grad = x->grad_del_u;
+    const bool dev_grad = (x->flags & FCAMD_EVAL_GRAD_ON_DEVICE) != 0;
+    const int flags = x->flags & ~FCAMD_EVAL_GRAD_ON_DEVICE;  // (the bit is kFlagTangentParamsHost inside a Launch)
     int st = validate_call(m, del_t, n, grad, x->stress_prev, x->stress, reinterpret_cast<const void* const*>(x->history_prev),
                            reinterpret_cast<const void* const*>(x->history), x->n_hist, flags);
     if (st != FCAMD_OK) return st;
     if ((st = check_protocol(m, n, x)) != FCAMD_OK) return st;
+    if (dev_grad && !aligned16(grad)) return fail(FCAMD_ERR_ALIGN, "device arrays must be 16-byte aligned");
     // The state's side of the whole call: device arrays, masks, per-point parameter fields (device arrays of n doubles), flags.  The
     // host side -- gradient, tangent, second stress store -- is filled in by the path the call takes; every launch is a slice of it.
     Launch L = launch_of(m, x);
-    L.grad = nullptr;
+    L.grad = dev_grad ? grad : nullptr;
+    L.flags = flags;
     L.counters = nullptr;  // the host entries count into the model's own counters and report them (stats)
     if ((st = check_fields(m, L.fields)) != FCAMD_OK) return st;
     fcamd_context* c = m->ctx;
@@ -835,13 +839,13 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
         return finish_single_stream(m, stats);
     }
     const size_t N = (size_t)n;
-    const size_t bytes_per_point = (GD2 + (stress_host ? SD : 0) + (tangent_host ? TD : 0)) * sizeof(double);
+    const size_t bytes_per_point = ((dev_grad ? 0 : GD2) + (stress_host ? SD : 0) + (tangent_host ? TD : 0)) * sizeof(double);
     // the tangent rebuilt on the CPU (fcamd_hosttangent.cpp) -- not under the sparse-tangent protocol, whose untouched rows stay as
     // they are in the caller's array, and for the 3-D laws' one-launch pass only
     ExpandPool* pool = host_tangent_for(m, n, tangent_host);
     if ((flags & FCAMD_EVAL_SPARSE_TANGENT) || m->dims.gdim != 3) pool = nullptr;
     if (L.fields) pool = nullptr;  // the host threads tile ONE tangent: with fields every point has its own, the kernel writes them
-    const bool all_registered = mapped(c, grad, N * GD2 * sizeof(double)) &&
+    const bool all_registered = (dev_grad || mapped(c, grad, N * GD2 * sizeof(double))) &&
                                 (!stress_host || mapped(c, stress_host, N * SD * sizeof(double))) &&
                                 (pool || !tangent_host || mapped(c, tangent_host, N * TD * sizeof(double)));
     // the host arrays of the pass: ranges the caller registered as they are, pageable ones page-locked for the
@@ -850,9 +854,9 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
     char *l_grad = nullptr, *l_stress = nullptr, *l_tan = nullptr;
     bool locked = false;
     if (all_registered || N * bytes_per_point > (size_t)c->opt.bounce_max) {
-        locked = arrays.lock(grad, N * GD2 * sizeof(double), &l_grad) &&
+        locked = (dev_grad || arrays.lock(grad, N * GD2 * sizeof(double), &l_grad)) &&
                  arrays.lock(stress_host, stress_host ? N * SD * sizeof(double) : 0, &l_stress);
-        if (locked && pool && !(c->opt.zero_copy_grad && aligned16(l_grad) && aligned16(l_stress))) pool = nullptr;  // no one-launch pass
+        if (locked && pool && !((dev_grad || (c->opt.zero_copy_grad && aligned16(l_grad))) && aligned16(l_stress))) pool = nullptr;  // no one-launch pass
         if (locked && !pool) locked = arrays.lock(tangent_host, tangent_host ? N * TD * sizeof(double) : 0, &l_tan);
         if (!locked) arrays.release();
     }
@@ -861,7 +865,7 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
         c->last_host_mode = FCAMD_HOST_BOUNCE;
         const int64_t chunk = bounce_chunk(c, n, bytes_per_point);
         BounceLayout lay;
-        const size_t o_grad = lay.take((size_t)chunk * GD2 * sizeof(double));
+        const size_t o_grad = dev_grad ? 0 : lay.take((size_t)chunk * GD2 * sizeof(double));
         const size_t o_stress = stress_host ? lay.take((size_t)chunk * SD * sizeof(double)) : 0;
         const size_t o_tan = tangent_host ? lay.take((size_t)chunk * TD * sizeof(double)) : 0;
         st = ensure_bounce(c, lay.used);
@@ -871,9 +875,11 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
         const bool second_store = stress_host && m->dims.gdim == 3;  // the 3-D kernels can store the stress twice
         for (int64_t p0 = 0; p0 < n; p0 += chunk) {
             const size_t np = (size_t)std::min<int64_t>(chunk, n - p0);
-            std::memcpy(c->bounce + o_grad, grad + GD2 * p0, np * GD2 * sizeof(double));
             Launch l = slice(m, L, p0);
-            l.grad = reinterpret_cast<const double*>(c->bounce_dev + o_grad);
+            if (!dev_grad) {
+                std::memcpy(c->bounce + o_grad, grad + GD2 * p0, np * GD2 * sizeof(double));
+                l.grad = reinterpret_cast<const double*>(c->bounce_dev + o_grad);
+            }
             if (tangent_host) l.tangent = reinterpret_cast<double*>(c->bounce_dev + o_tan);
             if (second_store) l.stress2 = reinterpret_cast<double*>(c->bounce_dev + o_stress);
             l.flags = flags & ~FCAMD_EVAL_SPARSE_TANGENT;  // the scratch holds no previous tangent: every row is written
@@ -891,9 +897,9 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
     }
     if (arrays.temp_locked()) c->last_host_mode |= FCAMD_HOST_TEMP_LOCK;
     const bool zc = zero_copy_enabled(c);
-    const double* z_grad = (zc && c->opt.zero_copy_grad && aligned16(l_grad)) ? reinterpret_cast<const double*>(l_grad) : nullptr;
+    const double* z_grad = dev_grad ? grad : ((zc && c->opt.zero_copy_grad && aligned16(l_grad)) ? reinterpret_cast<const double*>(l_grad) : nullptr);
     double* z_tan = (zc && tangent_host && aligned16(l_tan)) ? reinterpret_cast<double*>(l_tan) : nullptr;
-    c->last_host_mode |= (z_grad ? FCAMD_HOST_ZERO_COPY_IN : 0) | (z_tan ? FCAMD_HOST_ZERO_COPY_OUT : 0);
+    c->last_host_mode |= (z_grad && !dev_grad ? FCAMD_HOST_ZERO_COPY_IN : 0) | (z_tan ? FCAMD_HOST_ZERO_COPY_OUT : 0);
     // Everything the pass moves lies in page-locked caller memory and the law is a 3-D one (whose stress
     // store can feed two destinations): ONE launch reads the gradient from and writes stress and tangent
     // to the host arrays while it updates the device-resident state -- no chunks, no copies.
@@ -913,7 +919,7 @@ int fcamd_evaluate_resident(fcamd_model* m, double t, double del_t, int64_t n, c
         return finish_single_stream(m, stats);
     }
     int64_t chunk = 0;
-    st = prepare_chunks(c, grad, n, &chunk, /*staging=*/!(z_grad && (z_tan || !tangent_host)), /*locked=*/true);
+    st = prepare_chunks(c, dev_grad ? nullptr : grad, n, &chunk, /*staging=*/!(z_grad && (z_tan || !tangent_host)), /*locked=*/true);
     if (st != FCAMD_OK) return st;
     const int nslots = c->opt.host_slots;
     HIP_TRY(hipMemsetAsync(m->d_counters, 0, kCounterBytes, c->hstream[0]));

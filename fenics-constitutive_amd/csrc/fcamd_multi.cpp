@@ -607,6 +607,7 @@ int fcamd_multi_state_evaluate(fcamd_multi_state* st, double t, double del_t, co
                                double* tangent_host, int flags, fcamd_stats* stats) {
     if (!st) return fail(FCAMD_ERR_BAD_ARG, "state is NULL");
     fcamd_multi* mg = st->mg;
+    if (flags & FCAMD_EVAL_GRAD_ON_DEVICE) return fail(FCAMD_ERR_UNSUPPORTED, "FCAMD_EVAL_GRAD_ON_DEVICE is a flag of fcamd_evaluate_resident");
     if (flags & ~FCAMD_EVAL_SPARSE_TANGENT) return fail(FCAMD_ERR_BAD_ARG, "flags: FCAMD_EVAL_SPARSE_TANGENT or 0");
     if (st->n > 0 && !grad) return fail(FCAMD_ERR_BAD_ARG, "grad_del_u pointer is NULL");
     if (mg->info.needs_del_t && !(del_t > 0.0)) return fail(FCAMD_ERR_DEL_T, "Time step must be defined and positive.");

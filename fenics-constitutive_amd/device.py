@@ -48,6 +48,17 @@ def _check_torch(name: str, a):
     return a
 
 
+def _check_device_gradient(g, device_index: int):
+    """a gradient handed to a host-assembler entry as a device tensor (``DisplacementGradient``'s output): float64, contiguous,
+    on the state's device, 16-byte aligned"""
+    _check_torch("grad_del_u", g)
+    if (g.device.index or 0) != device_index:
+        raise ValueError(f"grad_del_u is on {g.device}, the state on cuda:{device_index}")
+    if g.data_ptr() % 16:
+        raise ValueError("grad_del_u must be 16-byte aligned")
+    return g
+
+
 def _current_stream_ptr(device_index: int) -> int:
     import torch
 

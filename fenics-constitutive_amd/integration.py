@@ -34,7 +34,29 @@ from .resident import ResidentState
 __all__ = ["use_resident_state", "use_resident_problem_state"]
 
 
-def use_resident_state(problem, sync_history: bool = True, pin: bool = True, direct_global: bool = True, devices=None) -> list:
+def _operators(problem, gradient_operators, devices) -> list:
+    """``gradient_operators`` as a list aligned with ``problem._law_on_submeshs`` (``None``: no law has one)"""
+    n = len(problem._law_on_submeshs)
+    if gradient_operators is None:
+        return [None] * n
+    ops = list(gradient_operators)
+    if len(ops) != n:
+        raise ValueError(f"gradient_operators has {len(ops)} entries, the problem {n} laws")
+    if devices is not None and any(op is not None for op in ops):
+        raise ValueError("gradient_operators: multi-device states take the gradient as an ndarray only")
+    return ops
+
+
+def _device_gradient(op, incr_disp, hold: list):
+    """the operator's gradient of the displacement increment ``current - previous``, written into the law's own device tensor
+    (``hold``: the one-element list of the patched ``evaluate`` that keeps it from call to call)"""
+    du = incr_disp.current.x.array - incr_disp.previous.x.array
+    hold[0] = op(du, out=hold[0])
+    return hold[0]
+
+
+def use_resident_state(problem, sync_history: bool = True, pin: bool = True, direct_global: bool = True, devices=None,
+                       gradient_operators=None) -> list:
     """Returns the created states (one per GPU-backed law of ``problem._law_on_submeshs``).
 
     ``devices`` (list of device ordinals): the single-process multi-GPU mode -- every law's state is a
@@ -45,9 +67,16 @@ def use_resident_state(problem, sync_history: bool = True, pin: bool = True, dir
     whole mesh: ``map_to_parent`` is ``parent.x.array[:] = sub.x.array[:]``, solver/maps.py:29-47) writes
     its stress and tangent straight into the problem's global arrays -- the host copy of 336 B per point
     and Newton iteration disappears as well (the law's local ``stress`` / ``local_tangent`` Functions are
-    then no longer updated)."""
+    then no longer updated).
+
+    ``gradient_operators``: a list aligned with ``problem._law_on_submeshs`` of ``DisplacementGradient`` operators (``None``
+    entries keep ``evaluate_local_incremental_gradient``).  A law with an operator forms ``incr_disp.current.x.array -
+    incr_disp.previous.x.array``, applies the operator on the GPU and hands the device tensor to ``evaluate_into``: the
+    nodal increment crosses the link instead of the gradient, and the law's ``displacement_gradient_fn`` is then no longer
+    filled (nor page-locked)."""
     states = []
-    for los in problem._law_on_submeshs:
+    operators = _operators(problem, gradient_operators, devices)
+    for los, op in zip(problem._law_on_submeshs, operators):
         law = los.law
         if not isinstance(law, DeviceLaw):
             continue
@@ -63,24 +92,30 @@ def use_resident_state(problem, sync_history: bool = True, pin: bool = True, dir
         else:
             state = ResidentState(law, n, stress0=stress0, history0=hist0)
         direct = bool(direct_global) and type(los.submesh_map).__name__ == "IdentityMap"
+        if op is not None and op.n_points != n:
+            raise ValueError(f"gradient operator of {op.n_points} points for a law of {n}")
         if pin:
             pinner = state if devices is not None else law  # one page lock for all devices of a multi-device state
+            grads = () if op is not None else (los.displacement_gradient_fn.x.array,)
             if direct:
-                pinner.pin_host_arrays(los.displacement_gradient_fn.x.array, problem.stress.current.x.array,
-                                       problem.tangent.x.array)
+                pinner.pin_host_arrays(*grads, problem.stress.current.x.array, problem.tangent.x.array)
             else:
-                pinner.pin_host_arrays(los.displacement_gradient_fn.x.array, los.stress.x.array, los.local_tangent.x.array)
+                pinner.pin_host_arrays(*grads, los.stress.x.array, los.local_tangent.x.array)
 
-        def evaluate(self, sim_time, incr_disp, global_stress, global_tangent, _state=state, _direct=direct):
-            incr_disp.evaluate_local_incremental_gradient(self.cells, self.displacement_gradient_fn)
+        hold = [None]  # this law's device gradient, kept from call to call
+
+        def evaluate(self, sim_time, incr_disp, global_stress, global_tangent, _state=state, _direct=direct, _op=op, _hold=hold):
+            if _op is None:
+                incr_disp.evaluate_local_incremental_gradient(self.cells, self.displacement_gradient_fn)
+                grad = self.displacement_gradient_fn.x.array
+            else:
+                grad = _device_gradient(_op, incr_disp, _hold)
             if _direct:
-                _state.evaluate_into(sim_time.current, sim_time.dt, self.displacement_gradient_fn.x.array,
-                                     global_stress.current.x.array, global_tangent.x.array)
+                _state.evaluate_into(sim_time.current, sim_time.dt, grad, global_stress.current.x.array, global_tangent.x.array)
                 global_stress.current.x.scatter_forward()  # what IdentityMap.map_to_parent does after its copy
                 global_tangent.x.scatter_forward()
                 return
-            _state.evaluate_into(sim_time.current, sim_time.dt, self.displacement_gradient_fn.x.array,
-                                 self.stress.x.array, self.local_tangent.x.array)
+            _state.evaluate_into(sim_time.current, sim_time.dt, grad, self.stress.x.array, self.local_tangent.x.array)
             self.map_to_parent(global_stress, global_tangent)
 
         def update_history(self, _state=state, _sync=sync_history, _multi=devices is not None):
@@ -114,7 +149,7 @@ def _parent_rows(los, n_local: int):
     return rows
 
 
-def use_resident_problem_state(problem, sync_history: bool = True, pin: bool = True, devices=None):
+def use_resident_problem_state(problem, sync_history: bool = True, pin: bool = True, devices=None, gradient_operators=None):
     """Multi-material form of ``use_resident_state``: ONE ``ResidentProblemState`` for all GPU-backed (FULL
     3-D) laws of ``problem`` -- the committed / trial stress of the whole mesh and every law's history on the
     GPU -- and every ``LawOnSubMesh.evaluate`` replaced by: incremental gradient (unchanged dolfinx call) ->
@@ -128,14 +163,20 @@ def use_resident_problem_state(problem, sync_history: bool = True, pin: bool = T
 
     ``devices`` (list of device ordinals): the same flow with ONE process driving several GPUs -- every law's points are
     cut into one contiguous slice per device (``multidevice.MultiDeviceProblemState``), each device writes its rows of
-    the global host arrays over its own PCIe link."""
+    the global host arrays over its own PCIe link.
+
+    ``gradient_operators``: as in ``use_resident_state`` -- a list aligned with ``problem._law_on_submeshs``; a law with an
+    operator gets its gradient from the GPU (``displacement_gradient_fn`` is then no longer filled)."""
+    operators = _operators(problem, gradient_operators, devices)
     gpu = [(i, los) for i, los in enumerate(problem._law_on_submeshs) if isinstance(los.law, DeviceLaw)]
     assert gpu, "no GPU-backed law in this problem"
     assert all(los.law.constraint.name == "FULL" for _, los in gpu), "use_resident_problem_state: FULL 3-D laws only"
     n = problem.stress.current.x.array.size // 6
     laws = []
-    for _, los in gpu:
+    for i, los in gpu:
         n_k = los.displacement_gradient_fn.x.array.size // 9
+        if operators[i] is not None and operators[i].n_points != n_k:
+            raise ValueError(f"gradient operator of {operators[i].n_points} points for a law of {n_k}")
         laws.append((los.law, _parent_rows(los, n_k)))
     single_identity = len(laws) == 1 and laws[0][1] is None
     if devices is not None:
@@ -153,16 +194,22 @@ def use_resident_problem_state(problem, sync_history: bool = True, pin: bool = T
     elif pin:
         first = gpu[0][1].law
         first.pin_host_arrays(problem.stress.current.x.array, problem.tangent.x.array)
-        for _, los in gpu:
-            los.law.pin_host_arrays(los.displacement_gradient_fn.x.array)
+        for i, los in gpu:
+            if operators[i] is None:
+                los.law.pin_host_arrays(los.displacement_gradient_fn.x.array)
     last = len(gpu) - 1
 
-    for k, (_, los) in enumerate(gpu):
-        def evaluate(self, sim_time, incr_disp, global_stress, global_tangent, _k=k):
-            incr_disp.evaluate_local_incremental_gradient(self.cells, self.displacement_gradient_fn)
+    for k, (i, los) in enumerate(gpu):
+        hold = [None]  # this law's device gradient, kept from call to call
+
+        def evaluate(self, sim_time, incr_disp, global_stress, global_tangent, _k=k, _op=operators[i], _hold=hold):
+            if _op is None:
+                incr_disp.evaluate_local_incremental_gradient(self.cells, self.displacement_gradient_fn)
+                grad = self.displacement_gradient_fn.x.array
+            else:
+                grad = _device_gradient(_op, incr_disp, _hold)
             state._time, state._del_t = sim_time.current, sim_time.dt
-            state.evaluate_law_into(_k, self.displacement_gradient_fn.x.array, global_stress.current.x.array,
-                                    global_tangent.x.array, sync=(_k == last))
+            state.evaluate_law_into(_k, grad, global_stress.current.x.array, global_tangent.x.array, sync=(_k == last))
             if _k == last:
                 global_stress.current.x.scatter_forward()  # as the reference's map_to_parent does per law
                 global_tangent.x.scatter_forward()

@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .device import DeviceLaw, _is_torch
+from .device import DeviceLaw, _check_device_gradient, _is_torch
 from .hostio import assign, to_device, to_host, upload
 
 
@@ -302,7 +302,7 @@ class ResidentProblemState:
                                         packed_masks=ls.packed_masks(self._c))
 
     # the host assembler's Newton-iteration call, law by law (LawOnSubMesh.evaluate, solver/_lawonsubmesh.py:72-95)
-    def evaluate_law_into(self, k: int, grad_del_u: np.ndarray, stress_parent: np.ndarray,
+    def evaluate_law_into(self, k: int, grad_del_u, stress_parent: np.ndarray,
                           tangent_parent: np.ndarray | None, sync: bool = True) -> None:
         """Law ``k`` only: trial state <- law(committed state, ``grad_del_u``) with the law's LOCAL gradient
         as a NumPy array, and the law's rows of the host assembler's PARENT arrays ``stress_parent`` (6 n)
@@ -312,16 +312,22 @@ class ResidentProblemState:
         (``law.pin_host_arrays`` / ``Context.register_host_buffer``) and are taken to be left alone between
         calls, as in ``ResidentState.evaluate_into``: constant tangents are written once per ``del_t``,
         point-dependent ones row by row (sparse tangent).  A page-locked gradient array is read in place,
-        a pageable one is uploaded first.  ``sync=False`` returns after the launch (several laws in flight;
+        a pageable one is uploaded first; a float64 device tensor on the state's device (the output of a
+        ``DisplacementGradient``) is read where it is.  ``sync=False`` returns after the launch (several laws in flight;
         the last call of a Newton iteration must synchronise before the host reads the arrays)."""
         import torch
 
         from . import _capi
-        from .device import _check_numpy, _current_stream_ptr
+        from .device import _check_numpy, _current_stream_ptr, _size
 
         ls = self._laws[k]
-        _check_numpy("grad_del_u", grad_del_u), _check_numpy("stress_parent", stress_parent)
-        assert grad_del_u.size == 9 * ls.n, "grad_del_u has the wrong length"
+        dev_grad = _is_torch(grad_del_u)
+        if dev_grad:
+            _check_device_gradient(grad_del_u, self.device.index or 0)
+        else:
+            _check_numpy("grad_del_u", grad_del_u)
+        _check_numpy("stress_parent", stress_parent)
+        assert _size(grad_del_u) == 9 * ls.n, "grad_del_u has the wrong length"
         assert stress_parent.size == 6 * self.n, "stress_parent has the wrong length"
         dev = self.device.index or 0
         m = ls.law._handle(dev)
@@ -338,13 +344,16 @@ class ResidentProblemState:
             # device arrays and copy this law's rows down -- correct for any array, meant for small problems
             self._evaluate_law_staged(k, grad_del_u, stress_parent, tangent_parent)
             return
-        try:
-            gptr = ctx.device_pointer(grad_del_u)
-        except ValueError:  # pageable gradient: upload
-            if ls.grad is None:
-                ls.grad = torch.empty(9 * ls.n, **self._f)
-            upload(ls.grad, grad_del_u)
-            gptr = ls.grad.data_ptr()
+        if dev_grad:
+            gptr = grad_del_u.data_ptr()
+        else:
+            try:
+                gptr = ctx.device_pointer(grad_del_u)
+            except ValueError:  # pageable gradient: upload
+                if ls.grad is None:
+                    ls.grad = torch.empty(9 * ls.n, **self._f)
+                upload(ls.grad, grad_del_u)
+                gptr = ls.grad.data_ptr()
         flags, target = 0, None if tptr is None else ("host", tptr, tangent_parent.nbytes)
         key = None
         if tptr is not None and ls.const_tangent and self.reuse_constant_tangent:
@@ -379,9 +388,13 @@ class ResidentProblemState:
         import torch
 
         ls = self._laws[k]
-        if ls.grad is None:
-            ls.grad = torch.empty(9 * ls.n, **self._f)
-        upload(ls.grad, grad_del_u)
+        if _is_torch(grad_del_u):
+            grad = grad_del_u.view(-1)
+        else:
+            if ls.grad is None:
+                ls.grad = torch.empty(9 * ls.n, **self._f)
+            upload(ls.grad, grad_del_u)
+            grad = ls.grad
         hp = None if ls.hist is None else ls.hist[self._c]
         hc = None if ls.hist is None else ls.hist[1 - self._c]
         ls.tangent_key = ls.host_tangent_key = None
@@ -390,13 +403,13 @@ class ResidentProblemState:
         tan = None if tangent_parent is None else self.tangent
         ls.stats_pending = ls.counters is not None
         if ls.rows is None:
-            ls.law.evaluate_from(self._time, self._del_t, ls.grad, self.stress_0, self.stress_1, tan, hp, hc,
+            ls.law.evaluate_from(self._time, self._del_t, grad, self.stress_0, self.stress_1, tan, hp, hc,
                                  history_mask=ls.mask, counters=ls.counters, packed_masks=ls.packed_masks(self._c))
             assign(stress_parent, self.stress_1)
             if tan is not None:
                 assign(tangent_parent, tan)
         else:
-            ls.law.evaluate_indexed(self._time, self._del_t, ls.grad, self.stress_0, self.stress_1, tan, ls.rows, hp, hc,
+            ls.law.evaluate_indexed(self._time, self._del_t, grad, self.stress_0, self.stress_1, tan, ls.rows, hp, hc,
                                     history_mask=ls.mask, counters=ls.counters, packed_masks=ls.packed_masks(self._c))
             rows = ls.rows.long()
             rows_h = to_host(rows)

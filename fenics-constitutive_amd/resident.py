@@ -426,7 +426,7 @@ class ResidentState:
         self.evaluate(t, del_t, g)
         return info
 
-    def evaluate_into(self, t: float, del_t: float, grad_del_u: np.ndarray, stress: np.ndarray | None = None,
+    def evaluate_into(self, t: float, del_t: float, grad_del_u, stress: np.ndarray | None = None,
                       tangent: np.ndarray | None = None):
         """The host assembler's Newton-iteration call: trial state <- law(committed state,
         grad_del_u) with ``grad_del_u`` a NumPy array, and the trial stress / tangent written into
@@ -439,12 +439,19 @@ class ResidentState:
         written from the second call on (``sparse_tangent``).  Construct the state with
         ``reuse_constant_tangent=False`` / ``sparse_tangent=False`` if the array is modified in between.
         Page-lock the three arrays once (``law.pin_host_arrays`` / ``Context.register_host_buffer``): the
-        kernel then reads the gradient from and writes the tangent to them directly."""
+        kernel then reads the gradient from and writes the tangent to them directly.
+        ``grad_del_u`` may also be a float64 device tensor on the state's device -- the output of a
+        ``DisplacementGradient`` -- which every launch of the call reads where it is
+        (``FCAMD_EVAL_GRAD_ON_DEVICE``): no gradient crosses the link."""
         from . import _capi
-        from .device import _check_numpy
+        from .device import _check_device_gradient, _check_numpy, _size
 
-        _check_numpy("grad_del_u", grad_del_u)
-        assert grad_del_u.size == self._gd2 * self.n, "grad_del_u has the wrong length"
+        dev_grad = _is_torch(grad_del_u)
+        if dev_grad:
+            _check_device_gradient(grad_del_u, self.device.index or 0)
+        else:
+            _check_numpy("grad_del_u", grad_del_u)
+        assert _size(grad_del_u) == self._gd2 * self.n, "grad_del_u has the wrong length"
         if stress is not None:
             _check_numpy("stress", stress)
             assert stress.size == self._sd * self.n, "stress has the wrong length"
@@ -483,11 +490,13 @@ class ResidentState:
             flags |= _capi.EVAL_SPLIT_HISTORY
         if self._packed:
             flags |= _capi.EVAL_PACKED_HISTORY
+        if dev_grad:
+            flags |= _capi.EVAL_GRAD_ON_DEVICE
         self._tangent_target = None
         self._stats_pending = False  # synchronous: the call itself reports
         try:
             self.law.last_stats = m.evaluate_resident(
-                t, del_t, self.n, grad_del_u.ctypes.data, self.stress_committed.data_ptr(), self.stress.data_ptr(),
+                t, del_t, self.n, grad_del_u.data_ptr() if dev_grad else grad_del_u.ctypes.data, self.stress_committed.data_ptr(), self.stress.data_ptr(),
                 hp, hc, None if self._mask is None else self._mask.data_ptr(),
                 None if stress is None else stress.ctypes.data, None if tangent is None else tangent.ctypes.data, flags,
                 packed_mask_ptrs=(self._ever[self._c].data_ptr(), self._ever[1 - self._c].data_ptr()) if self._packed else None,

@@ -300,6 +300,14 @@ typedef struct fcamd_eval_args {
    it.  Refused with FCAMD_ERR_UNSUPPORTED, nothing launched: the other laws and constraints, parent_rows, the wrapper form and
    fcamd_evaluate_batch; a misaligned field: FCAMD_ERR_ALIGN. */
 #define FCAMD_EVAL_PARAM_FIELDS 16
+/* fcamd_evaluate_resident only: `state->grad_del_u` is a 16-byte-aligned DEVICE array (gd2*n doubles) -- the output of a
+   gradient producer that ran on the device (fenics_constitutive_amd.DisplacementGradient) -- instead of the host gradient.
+   Every launch of the call reads it in place: it is neither looked up among the registered ranges, page-locked, copied nor
+   uploaded, the scratch / chunk decisions count the host outputs only, and FCAMD_HOST_ZERO_COPY_IN stays clear in
+   fcamd_context_last_host_mode.  A misaligned pointer: FCAMD_ERR_ALIGN.  fcamd_evaluate_device_ex, fcamd_evaluate_batch and
+   the multi-GPU entries (whose gradient is a device array or a host array by definition) refuse the flag with
+   FCAMD_ERR_UNSUPPORTED.  An additive flag of ABI 0.5: no entry, no struct member. */
+#define FCAMD_EVAL_GRAD_ON_DEVICE 32
 FCAMD_API int fcamd_evaluate_device_ex(fcamd_model* model, double t, double del_t, int64_t n,
                                        const fcamd_eval_args* args);
 
@@ -327,7 +335,7 @@ FCAMD_API int fcamd_evaluate_batch(int count, fcamd_model* const* models, const 
    up and 336 B/pt down instead of 176 + 392, and no host-side state copies.
    `state` describes the device-resident arrays exactly as for fcamd_evaluate_device_ex -- stress_prev / stress,
    history_prev / history, n_hist, history_mask, flags, packed_mask_prev / packed_mask -- with ONE difference:
-   `state->grad_del_u` is the HOST gradient array; tangent, parent_rows, stress2, wrapper_constraint must be NULL / 0 and
+   `state->grad_del_u` is the HOST gradient array (with FCAMD_EVAL_GRAD_ON_DEVICE: a device array, read in place); tangent, parent_rows, stress2, wrapper_constraint must be NULL / 0 and
    `counters` is ignored (the call is synchronous and reports through `stats`).
    The host arrays are handled as in fcamd_evaluate_host: ranges registered with
    fcamd_register_host_buffer as they are, pageable arrays page-locked for the duration of the call
