@@ -93,6 +93,22 @@ def inverse_jacobians(cell_coordinates, geometry_reference_gradients) -> np.ndar
     return inv[:, 0].copy() if dn.shape[0] == 1 else inv
 
 
+def integration_weights(cell_coordinates, geometry_reference_gradients, reference_weights) -> np.ndarray:
+    """``weights[c][q] = reference_weights[q] * |det J[c][q]|`` of an isoparametric mesh, in plain NumPy: what ``InternalForce``
+    multiplies every point's contribution with.  ``cell_coordinates`` and ``geometry_reference_gradients`` as for
+    ``inverse_jacobians()`` (tabulated at all Q points, or at one for an affine mesh); ``reference_weights[Q]``: the quadrature
+    weights on the reference cell."""
+    x = np.asarray(cell_coordinates, dtype=np.float64)
+    dn = np.asarray(geometry_reference_gradients, dtype=np.float64)
+    w = np.asarray(reference_weights, dtype=np.float64)
+    if x.ndim != 3 or dn.ndim != 3 or x.shape[1] != dn.shape[1] or x.shape[2] != dn.shape[2]:
+        raise ValueError(f"cell_coordinates [C][G][D] and geometry_reference_gradients [Q][G][D] do not match: {x.shape}, {dn.shape}")
+    if w.ndim != 1 or dn.shape[0] not in (1, w.shape[0]):
+        raise ValueError(f"reference_weights must be [Q] with Q = {dn.shape[0]} (or any Q for a tabulation at one point), got {w.shape}")
+    det = np.abs(np.linalg.det(np.einsum("cgx,qgk->cqxk", x, dn)))  # [c][q or 1]
+    return np.ascontiguousarray(det * w[None, :])
+
+
 #: corner signs of the trilinear hexahedron on [-1, 1]^3, in the node order of ``hex8_reference_gradients``
 HEX8_SIGNS = ((-1, -1, -1), (1, -1, -1), (1, 1, -1), (-1, 1, -1), (-1, -1, 1), (1, -1, 1), (1, 1, 1), (-1, 1, 1))
 

@@ -169,22 +169,29 @@ class CodeObject:
         self.key = key  # the compile cache key
         self.kernel = kernel
         self.resources = parse_resources(log)
-        self._functions = {}  # device -> (module, function)
+        self._modules = {}  # device -> module
+        self._functions = {}  # (device, kernel) -> function
         self._lock = threading.Lock()
 
-    def function(self, device: int):
+    def function(self, device: int, kernel: str | None = None):
+        """the function of ``kernel`` (default: the code object's own) in the module loaded on ``device``"""
+        kernel = kernel or self.kernel
         with self._lock:
-            f = self._functions.get(device)
+            f = self._functions.get((device, kernel))
             if f is None:
                 import torch
 
                 hip = _load_hip()
-                module, fn = C.c_void_p(), C.c_void_p()
+                module = self._modules.get(device)
+                fn = C.c_void_p()
                 with torch.cuda.device(device):
-                    hip_check(hip.hipModuleLoadData(C.byref(module), C.c_char_p(self.code)), "hipModuleLoadData")
-                    hip_check(hip.hipModuleGetFunction(C.byref(fn), module, self.kernel.encode()), "hipModuleGetFunction")
-                f = self._functions[device] = (module, fn)
-            return f[1]
+                    if module is None:
+                        module = C.c_void_p()
+                        hip_check(hip.hipModuleLoadData(C.byref(module), C.c_char_p(self.code)), "hipModuleLoadData")
+                        self._modules[device] = module
+                    hip_check(hip.hipModuleGetFunction(C.byref(fn), module, kernel.encode()), "hipModuleGetFunction")
+                f = self._functions[(device, kernel)] = fn
+            return f
 
 
 def include_closure(program: str) -> list:
@@ -285,12 +292,13 @@ def num_cu(device: int) -> int:
     return n
 
 
-def launch(code: CodeObject, device: int, blocks: int, args, what: str) -> None:
-    """``code``'s kernel over ``blocks`` blocks of 256 threads, the ctypes structure ``args`` its only parameter, on torch's
-    current stream of ``device`` (asynchronous); ``what`` names the launch in an error"""
+def launch(code: CodeObject, device: int, blocks: int, args, what: str, kernel: str | None = None) -> None:
+    """``code``'s kernel (``kernel``: another kernel of the same program) over ``blocks`` blocks of 256 threads, the ctypes
+    structure ``args`` its only parameter, on torch's current stream of ``device`` (asynchronous); ``what`` names the launch in an
+    error"""
     import torch
 
-    fn = code.function(device)
+    fn = code.function(device, kernel)
     params = (C.c_void_p * 1)(C.cast(C.pointer(args), C.c_void_p))
     with torch.cuda.device(device):
         hip_check(_load_hip().hipModuleLaunchKernel(fn, blocks, 1, 1, 256, 1, 1, 0, C.c_void_p(_current_stream_ptr(device)),
