@@ -24,6 +24,7 @@ from .userlaw import UserLaw, UserLawCompileError  # noqa: F401
 from .objective import JaumannRate  # noqa: F401
 from .gradient import DisplacementGradient  # noqa: F401
 from .force import InternalForce  # noqa: F401
+from .matrix import TangentMatrix  # noqa: F401
 from .wrappers import PlaneStrainFrom3D, PlaneStressFrom3D, UniaxialStrainFrom3D, UniaxialStressFrom3D  # noqa: F401
 from .utils import get_elastic_tangent, get_identity, lame_parameters, strain_from_grad_u  # noqa: F401
 
@@ -49,6 +50,7 @@ __all__ = [
     "JaumannRate",
     "DisplacementGradient",
     "InternalForce",
+    "TangentMatrix",
     "lame_parameters",
     "get_elastic_tangent",
     "get_identity",
