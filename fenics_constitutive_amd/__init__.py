@@ -11,4 +11,8 @@ import os as _os
 __path__ = [_os.path.join(_os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))), "fenics-constitutive_amd")]
 
 from ._api import *  # noqa: E402,F401,F403
-from ._api import __all__, __version__  # noqa: E402,F401
+from ._api import __all__ as _api_all  # noqa: E402
+from ._api import __version__  # noqa: E402,F401
+from .solver import ConjugateGradient  # noqa: E402,F401
+
+__all__ = [*_api_all, "ConjugateGradient"]
