@@ -2,7 +2,9 @@
 // device, K the values a TangentMatrix wrote (block CSR or scalar CSR over the same pattern).  Read at run time and compiled with
 // hiprtc behind the generated definitions:
 //   FCAMD_CG_D        dofs per node: 1, 2 or 3 (the blocks are D x D)
-//   FCAMD_CG_PRECOND  1: z = M^-1 r with the inverses of the nodes' own blocks (block-Jacobi); 0: z is r and rz is rr
+//   FCAMD_CG_PRECOND  1: z = M^-1 r with the inverses of the nodes' own blocks (block-Jacobi); 0: z is r and rz is rr; 2: z and rz
+//                     come from outside (multilevel.hip: the cycle's kernels and its closing kernel run between the update and
+//                     the direction kernel); the update kernel forms neither
 //   FCAMD_CG_SLAB     doubles of values a wave holds in its LDS region at a time (a multiple of 128)
 //
 // Five kernels, 256-thread blocks, all on one stream; every one reads what it needs from the Control block in device memory and
@@ -44,7 +46,8 @@ namespace fcamd_cg {
 using namespace fcamd;
 
 constexpr int D = FCAMD_CG_D, DD = D * D;
-constexpr bool kPrecond = FCAMD_CG_PRECOND != 0;
+constexpr bool kPrecond = FCAMD_CG_PRECOND == 1;
+constexpr bool kExternal = FCAMD_CG_PRECOND == 2;
 constexpr int kSeg = 3072;
 constexpr int kPerLane = kSeg / kBlock;  // 12
 constexpr int kSlab = FCAMD_CG_SLAB;
@@ -57,7 +60,7 @@ static_assert(kSlab % (2 * kWave) == 0 && kSlab >= 2 * kWave, "slab");
 static_assert((kWavesPerBlock * kSlab + kBlock + 2) * 8 <= 64 * 1024, "slab too large for the LDS of a block");
 
 enum Status : int { kRunning = 0, kConverged = 1, kMaxiter = 2, kIndefinite = 3, kSingular = 4, kNonfinite = 5 };
-enum Mode : int { kStart = 0, kIterate = 1, kPlain = 2 };
+enum Mode : int { kStart = 0, kIterate = 1, kPlain = 2, kQuiet = 3 };
 
 // the control block in device memory; solver.py mirrors the layout
 struct Control {
@@ -206,13 +209,15 @@ __device__ __forceinline__ double wave_rows(const Args& a, double* region, long 
 
 }  // namespace fcamd_cg
 
-// q = K va; mode kIterate: the status is honoured and pq <= 0 (or NaN) ends the solve; kPlain: the product and sc->dot = va . q
+// q = K va; mode kIterate: the status is honoured and pq <= 0 (or NaN) ends the solve; kPlain: the product and sc->dot = va . q;
+// kQuiet: the status is honoured and the product is all (no dot, no counter: the products of the multilevel cycle)
 extern "C" __global__ void __launch_bounds__(fcamd::kBlock) fcamd_cg_matvec_kernel(const fcamd_cg::Args a) {
     using namespace fcamd_cg;
     __shared__ __attribute__((aligned(16))) double slab[kWavesPerBlock][kSlab];
     __shared__ double red[kBlock + 2];
     Control* sc = a.sc;
     if (a.mode == kIterate && sc->status != kRunning) return;
+    if (a.mode == kQuiet && sc->status != kRunning) return;
     const int t = (int)threadIdx.x;
     const int lane = t & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(t / kWave);
@@ -230,9 +235,11 @@ extern "C" __global__ void __launch_bounds__(fcamd::kBlock) fcamd_cg_matvec_kern
                 acc = acc + a.va[g0 + lane] * qv;
             }
         }
+        if (a.mode == kQuiet) continue;  // (the same for the whole grid: no tree, no partial)
         const double total = block_tree(acc, red, t);
         if (t == 0) a.partials[seg] = total;
     }
+    if (a.mode == kQuiet) return;
     if (last_block(sc, red, t)) {
         const double pq = final_sum(a.partials, a.nseg, red, t);
         if (t == 0) {
@@ -269,7 +276,7 @@ extern "C" __global__ void __launch_bounds__(fcamd::kBlock) fcamd_cg_update_kern
                     rn = be;
                     if (a.has_x0) rn = be - a.q[e];
                     abb = abb + be * be;
-                    if (!kPrecond) a.p[e] = rn;
+                    if (!kPrecond && !kExternal) a.p[e] = rn;
                 } else {
                     a.x[e] = a.x[e] + alpha * a.p[e];
                     rn = a.r[e] - alpha * a.q[e];
@@ -321,10 +328,12 @@ extern "C" __global__ void __launch_bounds__(fcamd::kBlock) fcamd_cg_update_kern
                 const double r2 = sc->rtol * sc->rtol * bb, a2 = sc->atol * sc->atol;
                 sc->bb = bb;
                 sc->thr2 = r2 > a2 ? r2 : a2;
-                sc->rz = rz;
+                if (!kExternal) sc->rz = rz;
             } else {
-                sc->rz_old = sc->rz;
-                sc->rz = rz;
+                if (!kExternal) {
+                    sc->rz_old = sc->rz;
+                    sc->rz = rz;
+                }
                 sc->iterations = sc->iterations + 1;
             }
             if (sc->status == kRunning) {
@@ -345,7 +354,7 @@ extern "C" __global__ void __launch_bounds__(fcamd::kBlock) fcamd_cg_direction_k
     const Control* sc = a.sc;
     if (sc->status != kRunning) return;
     const double beta = sc->rz / sc->rz_old;
-    const double* z = kPrecond ? a.z : a.r;
+    const double* z = (kPrecond || kExternal) ? a.z : a.r;
     const long long stride = (long long)gridDim.x * kBlock;
     for (long long e = (long long)blockIdx.x * kBlock + threadIdx.x; e < a.n; e += stride) a.p[e] = z[e] + beta * a.p[e];
 }

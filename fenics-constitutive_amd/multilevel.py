@@ -1,0 +1,485 @@
+"""An aggregation multilevel preconditioner for the device solver: ``z = M^-1 r`` over a hierarchy of node aggregates with Galerkin
+coarse matrices, applied on the GPU inside ``ConjugateGradient`` (``preconditioner="multilevel"`` or an instance).
+
+*The hierarchy* is built once per pattern on the host (NumPy, no values involved, deterministic).  Aggregation works on the node
+graph of a level's block pattern; a row's neighbours are its column nodes, itself included.  Pass 1, nodes ascending: a node whose
+neighbours are all unaggregated becomes a root and its whole neighbourhood the next aggregate.  Pass 2: every node still free
+joins the aggregate of its lowest-numbered neighbour that pass 1 aggregated (the state after pass 1, not one updated on the way).
+Pass 3: what is left -- a node with no neighbour but itself -- is an aggregate of its own.  Aggregates are numbered in order of
+creation.  The coarse pattern is ``{(agg[i], agg[j])}`` over the fine blocks, block CSR with sorted columns whatever the format of
+``K``; coarse blocks stay ``D x D`` (piecewise-constant translation aggregates), so every level is multiplied by the solver's
+matrix-vector kernel and its nodes' own blocks are inverted by the solver's inverse kernel.  Levels are added until one has at
+most ``coarsest_nodes`` nodes, ``max_levels`` is reached or a level does not shrink.
+
+*The arithmetic* is fixed as in ``solver.py`` (no floating-point atomics, no MFMA, ``-ffp-contract=off``, ``/`` is a division), so
+a NumPy oracle gives the bits:
+
+*Galerkin values*, every call, level ``l + 1`` from level ``l``: for coarse block ``(I, J)`` and entry ``(r, s)``: ``f = 0.0; f = f +
+value_l(k, r, s)`` over the fine blocks ``k`` that fold into it, ascending; level 0's value sits where ``dest_base`` / ``dest_stride``
+of the ``TangentMatrix`` say (both formats: the same bits).  Constrained dofs are not special: their identity rows add ``1.0`` per
+constrained member to a coarse diagonal, which keeps a fully constrained aggregate non-singular and ``M`` symmetric positive
+definite.  *Block inverses* of every level: the solver's formulas; a zero or non-finite determinant on any level: status
+``singular_block``.  *Restriction*: ``rc[D I + c] = 0.0; rc = rc + d[D i + c]`` over the members ``i`` of ``I``, ascending; ``d`` is the
+level's right-hand side (additive) or ``b[e] - q[e]`` formed in the same kernel (multiplicative).  *Prolongation*: ``x[D i + c] =
+x[D i + c] + xc[D agg[i] + c]``, on level 0 skipped at the dofs of ``K.set_constrained`` (the mask the matrix carries at the call).
+*Smoothing sweep*: from zero ``x = omega * t``, later ``x = x + omega * t``, ``t = 0.0; t = t + inv[v][c][s] * d[D v + s]``, ``s``
+ascending, ``d = b`` or ``b - q``, ``q = K x`` by the matrix-vector kernel.
+
+*Additive cycle*: going down ``z_l = D_l^-1 r_l`` (no ``omega``: ``x = t``), ``r_{l+1} = R r_l``; on the coarsest level
+``coarsest_sweeps`` damped sweeps from zero; going up ``z_l = z_l + P z_{l+1}``.  *Multiplicative cycle*, per level: ``smoothing``
+sweeps from zero, ``q = K_l x``, restrict ``b - q``, recurse, prolong, ``smoothing`` sweeps; the coarsest level as in the additive
+cycle.  With one level both cycles are the coarsest sweeps on ``K`` itself.
+
+*In the conjugate gradients* the update kernel (``FCAMD_CG_PRECOND = 2``) forms neither ``z`` nor ``rz``; the cycle's launches and
+the closing kernel follow it: ``rz' = r . z`` by the solver's ordered dot, ``rz_old = rz``, ``rz = rz'`` (in the start: ``p = z``), and
+not ``rz > 0``: status ``indefinite`` (the iteration has been counted).  Every kernel returns at once when the status is not
+"running", so iterations enqueued behind the end are no-ops and ``check_every`` changes no bit.
+
+THE MULTIPLICATIVE CYCLE AND THE COARSEST SWEEPS NEED ``omega * lambda_max(D^-1 K) < 2``; nothing is refused for it and nothing
+estimates ``lambda_max``.  On the trilinear hexahedron cube it is 2.87, hence the default ``omega = 0.5``.
+
+LDS of a block: ``lds_bytes(kernel)``.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import jit, solver
+from .force import kernel_resources
+from .gradient import BLOCKS_PER_CU
+from .matrix import TangentMatrix
+
+GALERKIN_KERNEL = "fcamd_ml_galerkin_kernel"
+RESTRICT_KERNEL = "fcamd_ml_restrict_kernel"
+PROLONG_KERNEL = "fcamd_ml_prolong_kernel"
+SMOOTH_KERNEL = "fcamd_ml_smooth_kernel"
+CLOSE_KERNEL = "fcamd_ml_close_kernel"
+KERNELS = (GALERKIN_KERNEL, RESTRICT_KERNEL, PROLONG_KERNEL, SMOOTH_KERNEL, CLOSE_KERNEL)
+CYCLES = ("multiplicative", "additive")
+_MODE_QUIET = 3
+
+__all__ = ["MultilevelPreconditioner", "aggregate", "coarsen", "compile_kernels", "hierarchy", "lds_bytes", "program"]
+
+
+def lds_bytes(kernel: str = CLOSE_KERNEL) -> int:
+    """LDS of one block of ``kernel``: the tree of the dot and the last-block flag in the closing kernel, nothing in the other four;
+    the solver's kernels of the same program: ``solver.lds_bytes(kernel, False)``"""
+    if kernel in solver.KERNELS:
+        return solver.lds_bytes(kernel, False)
+    return {CLOSE_KERNEL: 8 * (256 + 2), GALERKIN_KERNEL: 0, RESTRICT_KERNEL: 0, PROLONG_KERNEL: 0, SMOOTH_KERNEL: 0}[kernel]
+
+
+def program(gdim: int, slab: int = solver.SLAB) -> str:
+    """the program text of one block size: the solver's kernels without their own preconditioner and the multilevel kernels"""
+    return "\n".join([f"#define FCAMD_CG_D {int(gdim)}", "#define FCAMD_CG_PRECOND 2", f"#define FCAMD_CG_SLAB {int(slab)}", '#include "multilevel.hip"']) + "\n"
+
+
+def compile_kernels(gdim: int):
+    """The code object of one block size, all ten kernels in it (no GPU needed).  A kernel with scratch is a ``ValueError``."""
+    if gdim not in (1, 2, 3):
+        raise ValueError(f"the dofs per node must be 1, 2 or 3, got {gdim}")
+    code = jit.compile_program(program(gdim), f"multilevel_{gdim}d", solver.MATVEC_KERNEL)
+    for kernel in solver.KERNELS + KERNELS:
+        scratch = kernel_resources(code.log, kernel)["scratch_bytes"]
+        if scratch:
+            raise ValueError(f"multilevel_{gdim}d: {kernel} compiles with {scratch} bytes of scratch per lane")
+    return code
+
+
+# ---- the hierarchy (host) --------------------------------------------------------------------------------------------------------
+def aggregate(indptr: np.ndarray, indices: np.ndarray):
+    """``(agg[n_nodes], roots)``: the aggregate of every node of the block pattern and the root of every aggregate (int32), by the
+    three passes of the module docstring"""
+    n = int(indptr.size - 1)
+    ptr, cols = indptr.tolist(), indices.tolist()
+    agg = [-1] * n
+    roots = []
+    for v in range(n):  # pass 1
+        nb = cols[ptr[v]: ptr[v + 1]]
+        if agg[v] >= 0 or any(agg[u] >= 0 for u in nb):
+            continue
+        for u in nb:
+            agg[u] = len(roots)
+        agg[v] = len(roots)
+        roots.append(v)
+    agg1 = np.array(agg, dtype=np.int64).reshape(n)
+    out = agg1.copy()
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr.astype(np.int64)))
+    cols = indices.astype(np.int64)
+    sel = np.flatnonzero((agg1[rows] < 0) & (agg1[cols] >= 0))  # pass 2 (the columns of a row ascend: the first is the lowest)
+    joiners, first = np.unique(rows[sel], return_index=True)
+    out[joiners] = agg1[cols[sel[first]]]
+    alone = np.flatnonzero(out < 0)  # pass 3
+    out[alone] = len(roots) + np.arange(alone.size)
+    return out.astype(np.int32), np.concatenate([np.array(roots, dtype=np.int64), alone]).astype(np.int32)
+
+
+def coarsen(indptr: np.ndarray, indices: np.ndarray, agg: np.ndarray, n_agg: int):
+    """``(indptr, indices, fold_ptr, fold)`` (int32): the coarse block CSR pattern ``{(agg[i], agg[j])}`` with sorted columns, and for
+    coarse block ``K`` the fine blocks ``fold[fold_ptr[K]: fold_ptr[K + 1]]`` that fold into it, ascending"""
+    rows = np.repeat(np.arange(indptr.size - 1, dtype=np.int64), np.diff(indptr.astype(np.int64)))
+    key = agg.astype(np.int64)[rows] * n_agg + agg.astype(np.int64)[indices]
+    order = np.argsort(key, kind="stable")  # stable: ascending fine block within a coarse block
+    pattern, counts = np.unique(key, return_counts=True)
+    c_indptr = np.zeros(n_agg + 1, dtype=np.int64)
+    np.cumsum(np.bincount(pattern // n_agg, minlength=n_agg), out=c_indptr[1:])
+    fold_ptr = np.zeros(pattern.size + 1, dtype=np.int64)
+    np.cumsum(counts, out=fold_ptr[1:])
+    return c_indptr.astype(np.int32), (pattern % n_agg).astype(np.int32), fold_ptr.astype(np.int32), order.astype(np.int32)
+
+
+class Level:
+    """one level's pattern and, unless it is the coarsest, the tables that lead to the next"""
+
+    def __init__(self, indptr, indices):
+        self.indptr, self.indices = indptr, indices
+        self.n_nodes, self.nnzb = int(indptr.size - 1), int(indices.size)
+        rows = np.repeat(np.arange(self.n_nodes, dtype=np.int32), np.diff(indptr.astype(np.int64)))
+        self.diag_block = np.full(self.n_nodes, -1, dtype=np.int64)
+        on = np.flatnonzero(indices == rows)
+        self.diag_block[rows[on]] = on
+        self.agg = self.roots = self.mem_ptr = self.members = self.fold_ptr = self.fold = None
+
+
+def hierarchy(indptr: np.ndarray, indices: np.ndarray, coarsest_nodes: int = 64, max_levels: int = 10) -> list:
+    """the levels of a block pattern, finest first"""
+    levels = [Level(np.ascontiguousarray(indptr, dtype=np.int32), np.ascontiguousarray(indices, dtype=np.int32))]
+    while levels[-1].n_nodes > coarsest_nodes and len(levels) < max_levels:
+        fine = levels[-1]
+        agg, roots = aggregate(fine.indptr, fine.indices)
+        if roots.size >= fine.n_nodes:
+            break  # it does not shrink
+        c_indptr, c_indices, fold_ptr, fold = coarsen(fine.indptr, fine.indices, agg, int(roots.size))
+        fine.agg, fine.roots, fine.fold_ptr, fine.fold = agg, roots, fold_ptr, fold
+        fine.members = np.argsort(agg, kind="stable").astype(np.int32)  # ascending within an aggregate
+        mem_ptr = np.zeros(roots.size + 1, dtype=np.int64)
+        np.cumsum(np.bincount(agg, minlength=roots.size), out=mem_ptr[1:])
+        fine.mem_ptr = mem_ptr.astype(np.int32)
+        levels.append(Level(c_indptr, c_indices))
+    return levels
+
+
+class Args(C.Structure):
+    """ctypes mirror of fcamd_ml::Args (multilevel.hip)"""
+
+    _fields_ = [(name, C.c_void_p) for name in ("fine_values", "coarse_values", "fold_ptr", "fold", "dest_base", "dest_stride", "mem_ptr", "members", "agg",
+                                                "mask", "b", "q", "x", "xc", "rc", "inv", "r", "z", "p", "partials", "sc")] + \
+               [("omega", C.c_double), ("n", C.c_int64), ("n_coarse", C.c_int64), ("nseg", C.c_int64),
+                ("first", C.c_int32), ("plain", C.c_int32), ("use_q", C.c_int32), ("start", C.c_int32)]
+
+
+class _OnDevice:
+    """the hierarchy's tables, values and vectors on one device"""
+
+    def __init__(self, pc, dev: int):
+        import torch
+
+        from .hostio import to_device
+
+        d = torch.device("cuda", dev)
+        dd, d_ = pc.K.gdim**2, pc.K.gdim
+
+        def zeros(n):
+            return torch.zeros(max(int(n), 2), dtype=torch.float64, device=d)
+
+        self.dummy = to_device(np.zeros(1, dtype=np.int32), d)
+        self.tables, self.values, self.inv, self.b, self.x, self.q = [], [None], [], [None], [None], []
+        for l, lv in enumerate(pc._levels):
+            t = {}
+            if l > 0:
+                t["indptr"], t["indices"] = to_device(lv.indptr, d), to_device(lv.indices, d)
+                t["diag"] = to_device(np.maximum(lv.diag_block, 0).astype(np.int32), d)
+                self.values.append(zeros(dd * lv.nnzb))
+                self.b.append(zeros(d_ * lv.n_nodes))
+                self.x.append(zeros(d_ * lv.n_nodes))
+            if lv.agg is not None:
+                for name in ("agg", "mem_ptr", "members", "fold_ptr", "fold"):
+                    t[name] = to_device(getattr(lv, name), d)
+            self.tables.append(t)
+            self.inv.append(zeros(dd * lv.n_nodes))
+            self.q.append(zeros(d_ * lv.n_nodes))
+        self.control = None  # of setup() and apply()
+        self.plan_key, self.plan, self.plan_holds = None, None, None
+
+
+class MultilevelPreconditioner:
+    """``MultilevelPreconditioner(K, cycle, smoothing, omega, coarsest_nodes, coarsest_sweeps, max_levels)``: the aggregation
+    multilevel preconditioner of ``K`` (a ``TangentMatrix`` in either format), for ``ConjugateGradient(K, preconditioner=...)``.
+
+    ``cycle``: "multiplicative" -- a V cycle with ``smoothing`` damped block-Jacobi sweeps before and after the coarse correction,
+    ``2 smoothing`` fine products per application (the first sweep starts from zero and needs none; one for the residual, one in
+    every later sweep) and the same on every coarse level -- or "additive" -- block-Jacobi on every level, no fine product.  ``omega``: the
+    damping of the sweeps (``omega * lambda_max(D^-1 K) < 2`` IS NEEDED AND NOT CHECKED, see the module docstring).  The hierarchy
+    stops at a level of at most ``coarsest_nodes`` nodes or at ``max_levels``; there ``coarsest_sweeps`` sweeps from zero stand for a
+    solve.  Built on the host at construction from the pattern alone, with the kernels compiled there (no GPU needed); a level
+    with a node without a diagonal block is refused.  ``levels``, ``aggregates(l)``, ``pattern(l)``, ``members(l)``, ``folds(l)`` and
+    ``roots(l)`` show the tables.  All value and vector tensors of the hierarchy belong to the object, one set per device,
+    allocated at the first call; use an object from one stream at a time."""
+
+    def __init__(self, K: TangentMatrix, cycle: str = "multiplicative", smoothing: int = 1, omega: float = 0.5, coarsest_nodes: int = 64,
+                 coarsest_sweeps: int = 8, max_levels: int = 10):
+        if not isinstance(K, TangentMatrix):
+            raise TypeError(f"K must be a TangentMatrix, got {type(K).__name__}")
+        if cycle not in CYCLES:
+            raise ValueError(f"cycle must be one of {CYCLES}, got {cycle!r}")
+        if isinstance(omega, bool) or not isinstance(omega, (int, float, np.integer, np.floating)):
+            raise TypeError(f"omega must be a number, got {type(omega).__name__}")
+        if not (omega > 0.0 and np.isfinite(omega)):
+            raise ValueError(f"omega must be finite and positive, got {omega}")
+        for name, v in (("smoothing", smoothing), ("coarsest_nodes", coarsest_nodes), ("coarsest_sweeps", coarsest_sweeps), ("max_levels", max_levels)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{name} must be an integer, got {type(v).__name__}")
+            if v < 1 or v >= 2**31:
+                raise ValueError(f"{name} must lie in [1, 2^31), got {v}")
+        missing = np.flatnonzero(K.diag_block < 0)
+        if missing.size:
+            raise ValueError(f"node {int(missing[0])} has no diagonal block in the pattern: its row is empty, the matrix singular")
+        self.K = K
+        # fixed for the life of the object (read-only properties below): the launch plan of a cycle is built from them
+        self._cycle_name, self._smoothing, self._omega = cycle, int(smoothing), float(omega)
+        self._coarsest_nodes, self._coarsest_sweeps, self._max_levels = int(coarsest_nodes), int(coarsest_sweeps), int(max_levels)
+        self._levels = hierarchy(K.indptr, K.indices, self.coarsest_nodes, self.max_levels)
+        for l, lv in enumerate(self._levels):
+            missing = np.flatnonzero(lv.diag_block < 0)
+            if missing.size:
+                raise ValueError(f"node {int(missing[0])} of level {l} has no diagonal block in the pattern")
+        self._op = solver._operator(K)
+        self._code = compile_kernels(K.gdim)
+        self._on = {}  # device index -> _OnDevice
+
+    # ---- what was asked for (read-only) ----------------------------------------------------------------------------------------
+    cycle = property(lambda self: self._cycle_name)
+    smoothing = property(lambda self: self._smoothing)
+    omega = property(lambda self: self._omega)
+    coarsest_nodes = property(lambda self: self._coarsest_nodes)
+    coarsest_sweeps = property(lambda self: self._coarsest_sweeps)
+    max_levels = property(lambda self: self._max_levels)
+
+    # ---- what was built --------------------------------------------------------------------------------------------------------
+    @property
+    def levels(self) -> list:
+        """``[{"nodes", "blocks"}]``, finest first"""
+        return [{"nodes": lv.n_nodes, "blocks": lv.nnzb} for lv in self._levels]
+
+    def _fine(self, l: int) -> Level:
+        if not 0 <= l < len(self._levels) - 1:
+            raise ValueError(f"level {l} has no coarser level (the hierarchy has {len(self._levels)})")
+        return self._levels[l]
+
+    def aggregates(self, l: int) -> np.ndarray:
+        """the aggregate (the node of level ``l + 1``) of every node of level ``l``"""
+        return self._fine(l).agg
+
+    def roots(self, l: int) -> np.ndarray:
+        """the root of every aggregate of level ``l`` (a lone node is its own)"""
+        return self._fine(l).roots
+
+    def members(self, l: int):
+        """``(mem_ptr, members)``: the members of every aggregate of level ``l``, ascending"""
+        return self._fine(l).mem_ptr, self._fine(l).members
+
+    def folds(self, l: int):
+        """``(fold_ptr, fold)``: for every block of level ``l + 1`` the blocks of level ``l`` that fold into it, ascending"""
+        return self._fine(l).fold_ptr, self._fine(l).fold
+
+    def pattern(self, l: int):
+        """``(indptr, indices)`` of level ``l``, block CSR"""
+        if not 0 <= l < len(self._levels):
+            raise ValueError(f"there is no level {l} (the hierarchy has {len(self._levels)})")
+        return self._levels[l].indptr, self._levels[l].indices
+
+    def diag_block(self, l: int) -> np.ndarray:
+        self.pattern(l)
+        return self._levels[l].diag_block
+
+    @property
+    def resources(self) -> dict:
+        """the compiler's remarks of the five multilevel kernels, by "galerkin", "restrict", "prolong", "smooth" and "close" """
+        return {kernel[len("fcamd_ml_"): -len("_kernel")]: kernel_resources(self._code.log, kernel) for kernel in KERNELS}
+
+    @property
+    def compile_log(self) -> str:
+        return self._code.log
+
+    @staticmethod
+    def lds_bytes(kernel: str = CLOSE_KERNEL) -> int:
+        return lds_bytes(kernel)
+
+    @property
+    def device(self) -> int:
+        return self.K.device
+
+    # ---- launches --------------------------------------------------------------------------------------------------------------
+    def _device(self, dev: int) -> _OnDevice:
+        on = self._on.get(dev)
+        if on is None:
+            import torch
+
+            with torch.cuda.device(dev):
+                on = self._on[dev] = _OnDevice(self, dev)
+        return on
+
+    def _level_args(self, dev: int, l: int, values, control) -> solver.Args:
+        """the solver's arguments of level ``l``: its matrix for the product and the inverse kernel"""
+        if l == 0:
+            a = self._op.args(dev, values, control)
+        else:
+            on, lv, t = self._device(dev), self._levels[l], self._device(dev).tables[l]
+            d_ = self.K.gdim
+            a = solver.Args()
+            a.values, a.indptr, a.indices, a.diag, a.groups = (on.values[l].data_ptr(), t["indptr"].data_ptr(), t["indices"].data_ptr(), t["diag"].data_ptr(),
+                                                               on.dummy.data_ptr())
+            a.partials, a.sc = control.partials.data_ptr(), control.device_block.data_ptr()
+            a.n, a.nnz, a.nseg, a.n_nodes, a.csr = d_ * lv.n_nodes, d_ * d_ * lv.nnzb, solver._segments(d_ * lv.n_nodes), lv.n_nodes, 0
+        a.inv = self._device(dev).inv[l].data_ptr()
+        return a
+
+    @staticmethod
+    def _blocks(n: int, cap: int) -> int:
+        return max(1, min(-(-n // 256), cap))
+
+    def _setup(self, dev: int, values, control) -> None:
+        """the Galerkin values of every coarse level, then the inverses of every level's own blocks (asynchronous)"""
+        on, cap, dd = self._device(dev), BLOCKS_PER_CU * jit.num_cu(dev), self.K.gdim**2
+        tables = self.K._tables(dev)
+        for l, lv in enumerate(self._levels[:-1]):
+            a = Args()
+            a.fine_values = (values if l == 0 else on.values[l]).data_ptr()
+            a.coarse_values = on.values[l + 1].data_ptr()
+            a.fold_ptr, a.fold = on.tables[l]["fold_ptr"].data_ptr(), on.tables[l]["fold"].data_ptr()
+            if l == 0:
+                a.dest_base, a.dest_stride = tables[2].data_ptr(), tables[3].data_ptr()
+            a.sc = control.device_block.data_ptr()
+            a.n_coarse = dd * self._levels[l + 1].nnzb
+            jit.launch(self._code, dev, self._blocks(a.n_coarse, cap), a, "MultilevelPreconditioner Galerkin launch", kernel=GALERKIN_KERNEL)
+        for l, lv in enumerate(self._levels):
+            jit.launch(self._code, dev, self._blocks(lv.n_nodes, cap), self._level_args(dev, l, values, control), "MultilevelPreconditioner inverse launch",
+                       kernel=solver.INVERSE_KERNEL)
+
+    def _plan(self, dev: int, values, control, r_ptr: int, z_ptr: int) -> list:
+        """the launches of one application ``z = M^-1 r``: ``[(kernel, blocks, args, what)]``"""
+        on, cap, d_ = self._device(dev), BLOCKS_PER_CU * jit.num_cu(dev), self.K.gdim
+        mask = self.K._mask_table(dev)
+        sc = control.device_block.data_ptr()
+        n_of = [d_ * lv.n_nodes for lv in self._levels]
+        b_of = [r_ptr] + [t.data_ptr() for t in on.b[1:]]
+        x_of = [z_ptr] + [t.data_ptr() for t in on.x[1:]]
+        q_of = [t.data_ptr() for t in on.q]
+        last = len(self._levels) - 1
+        ops = []
+
+        def product(l):
+            a = self._level_args(dev, l, values, control)
+            a.va, a.q, a.mode = x_of[l], q_of[l], _MODE_QUIET
+            ops.append((solver.MATVEC_KERNEL, max(1, min(int(a.nseg), cap)), a, "MultilevelPreconditioner matrix-vector launch"))
+
+        def smooth(l, first=0, plain=0, use_q=0):
+            a = Args()
+            a.b, a.q, a.x, a.inv, a.sc, a.omega, a.n = b_of[l], q_of[l], x_of[l], on.inv[l].data_ptr(), sc, self.omega, n_of[l]
+            a.first, a.plain, a.use_q = first, plain, use_q
+            ops.append((SMOOTH_KERNEL, self._blocks(n_of[l], cap), a, "MultilevelPreconditioner smoothing launch"))
+
+        def sweeps(l, count, from_zero):
+            for i in range(count):
+                if from_zero and i == 0:
+                    smooth(l, first=1)
+                else:
+                    product(l)
+                    smooth(l, use_q=1)
+
+        def restrict(l, use_q):
+            a, t = Args(), on.tables[l]
+            a.mem_ptr, a.members, a.b, a.q, a.rc, a.sc, a.n_coarse, a.use_q = t["mem_ptr"].data_ptr(), t["members"].data_ptr(), b_of[l], q_of[l], b_of[l + 1], sc, n_of[l + 1], use_q
+            ops.append((RESTRICT_KERNEL, self._blocks(n_of[l + 1], cap), a, "MultilevelPreconditioner restriction launch"))
+
+        def prolong(l):
+            a = Args()
+            a.agg, a.x, a.xc, a.sc, a.n = on.tables[l]["agg"].data_ptr(), x_of[l], x_of[l + 1], sc, n_of[l]
+            if l == 0 and mask is not None:
+                a.mask = mask.data_ptr()
+            ops.append((PROLONG_KERNEL, self._blocks(n_of[l], cap), a, "MultilevelPreconditioner prolongation launch"))
+
+        if self.cycle == "additive":
+            for l in range(last):
+                smooth(l, plain=1)
+                restrict(l, 0)
+            sweeps(last, self.coarsest_sweeps, True)
+            for l in range(last - 1, -1, -1):
+                prolong(l)
+        else:
+            for l in range(last):
+                sweeps(l, self.smoothing, True)
+                product(l)
+                restrict(l, 1)
+            sweeps(last, self.coarsest_sweeps, True)
+            for l in range(last - 1, -1, -1):
+                prolong(l)
+                sweeps(l, self.smoothing, False)
+        return ops
+
+    def _cycle(self, dev: int, values, control, r_ptr: int, z_ptr: int) -> None:
+        """``z = M^-1 r`` with the values ``_setup`` left (asynchronous)"""
+        on = self._device(dev)
+        mask = self.K._mask_table(dev)
+        # every device pointer the plan's arguments hold that is not the object's own: the values, the control block and its
+        # partial sums, the vectors, the mask and the level-0 tables.  The control and the mask are kept alive with the plan, so
+        # that their addresses cannot be handed to other tensors while it is cached.
+        key = (values.data_ptr(), control.device_block.data_ptr(), control.partials.data_ptr(), r_ptr, z_ptr, None if mask is None else mask.data_ptr(),
+               tuple(t.data_ptr() for t in self._op.tables(dev)), jit.num_cu(dev))
+        if on.plan_key != key:
+            on.plan, on.plan_key, on.plan_holds = self._plan(dev, values, control, r_ptr, z_ptr), key, (control, mask)
+        for kernel, blocks, a, what in on.plan:
+            jit.launch(self._code, dev, blocks, a, what, kernel=kernel)
+
+    def _close(self, dev: int, control, r, z, p, start: bool) -> None:
+        """the closing kernel behind a cycle: ``rz``, ``rz_old``, in the start ``p = z``"""
+        a = Args()
+        a.r, a.z, a.p, a.partials, a.sc = r.data_ptr(), z.data_ptr(), p.data_ptr(), control.partials.data_ptr(), control.device_block.data_ptr()
+        a.n, a.nseg, a.start = self._op.n, self._op.nseg, 1 if start else 0
+        jit.launch(self._code, dev, self._op.blocks(dev), a, "MultilevelPreconditioner closing launch", kernel=CLOSE_KERNEL)
+
+    def _own_control(self, dev: int):
+        on = self._device(dev)
+        if on.control is None:
+            on.control = solver._Control(dev, self._op.nseg)
+        on.control.upload()
+        return on.control
+
+    # ---- standalone --------------------------------------------------------------------------------------------------------------
+    def setup(self, values) -> list:
+        """The value tensors of the coarse levels (block CSR, ``[blocks][D][D]`` flat), finest first, formed from ``values`` with the
+        inverses of every level (asynchronous, on torch's current stream).  The tensors are the object's own: the next call writes
+        them again."""
+        import torch
+
+        dev = self.device
+        self.K._check("values", values, self.K.nnz, dev)
+        with torch.cuda.device(dev):
+            if self.K.shape[0]:
+                self._setup(dev, values, self._own_control(dev))
+            on = self._device(dev)
+            return [on.values[l][: self.K.gdim**2 * lv.nnzb] for l, lv in enumerate(self._levels) if l > 0]
+
+    def apply(self, values, r, out=None):
+        """``out = M^-1 r`` for the matrix ``values`` (asynchronous, on torch's current stream); ``out`` must not alias ``r``.  With a
+        singular block on any level nothing is applied and ``out`` is left as it was."""
+        import torch
+
+        dev, n = self.device, self.K.shape[0]
+        self.K._check("values", values, self.K.nnz, dev)
+        self.K._check("r", r, n, dev)
+        if out is not None:
+            self.K._check("out", out, n, dev)
+            if solver._overlap(out, r):
+                raise ValueError("out must not alias r")
+        with torch.cuda.device(dev):
+            if out is None:
+                out = torch.zeros(n, dtype=torch.float64, device=torch.device("cuda", dev))
+            if n:
+                control = self._own_control(dev)
+                self._setup(dev, values, control)
+                self._cycle(dev, values, control, r.data_ptr(), out.data_ptr())
+        return out

@@ -43,6 +43,11 @@ iterations of three launches (product, update, direction) and looks again: a loo
 status and count -- back through a page-locked buffer, and the host stops or enqueues the next batch (``SolveResult.looks``): iterations enqueued behind the end are no-ops, and
 the result is the same bits for every ``check_every``.  No cooperative launch, no grid-wide barrier, no kernel that waits on a flag.
 
+*Multilevel.*  With ``preconditioner="multilevel"`` (or a ``MultilevelPreconditioner`` of ``K``) the program is compiled with
+``FCAMD_CG_PRECOND = 2``: the update kernel forms neither ``z`` nor ``rz``; the cycle's launches and a closing kernel (``multilevel.py``)
+follow it in every iteration and in the start, and the coarse levels' products run in the matrix-vector kernel's mode 3, which
+honours the status and touches neither ``pq`` nor the counter.
+
 LDS of a block: ``lds_bytes(kernel)``; the same ``LDS_CAP`` as the other operators.
 """
 
@@ -326,7 +331,10 @@ class ConjugateGradient:
     """``cg(values, b, x0=None, out=None) -> SolveResult``: ``K x = b`` by preconditioned conjugate gradients on the GPU.
 
     ``K``: the ``TangentMatrix`` whose values array is solved with, in either format.  ``preconditioner``: "block_jacobi" -- the
-    inverses of the nodes' own blocks, formed from ``values`` at every call -- or ``None``.  The iteration stops at
+    inverses of the nodes' own blocks, formed from ``values`` at every call --, ``None``, or "multilevel" -- a
+    ``MultilevelPreconditioner(K)`` with its defaults -- or such an object built for the same ``K`` (multilevel.py: its Galerkin values
+    and inverses are formed at every call, its cycle and closing kernel run between the update and the direction kernel, and a
+    preconditioned residual with ``r . z`` not positive ends the solve as ``indefinite``).  The iteration stops at
     ``r . r <= max(rtol^2 b . b, atol^2)`` (the recurrence's residual) or after ``maxiter`` iterations (default ``10 D n_nodes``);
     ``check_every``: iterations enqueued between two looks at the status (the result does not depend on it).
 
@@ -342,8 +350,15 @@ class ConjugateGradient:
                  check_every: int = 16):
         if not isinstance(K, TangentMatrix):
             raise TypeError(f"K must be a TangentMatrix, got {type(K).__name__}")
-        if preconditioner not in PRECONDITIONERS:
-            raise ValueError(f"preconditioner must be one of {PRECONDITIONERS}, got {preconditioner!r}")
+        from .multilevel import MultilevelPreconditioner
+
+        if isinstance(preconditioner, str) and preconditioner == "multilevel":
+            pass  # built below, once everything else has been validated
+        elif isinstance(preconditioner, MultilevelPreconditioner):
+            if preconditioner.K is not K:
+                raise ValueError("the MultilevelPreconditioner was built for another matrix")
+        elif not (preconditioner is None or (isinstance(preconditioner, str) and preconditioner == "block_jacobi")):
+            raise ValueError(f"preconditioner must be one of {PRECONDITIONERS + ('multilevel',)} or a MultilevelPreconditioner of K, got {preconditioner!r}")
         for name, v in (("rtol", rtol), ("atol", atol)):
             if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
                 raise TypeError(f"{name} must be a number, got {type(v).__name__}")
@@ -360,11 +375,15 @@ class ConjugateGradient:
         missing = np.flatnonzero(K.diag_block < 0)
         if missing.size:
             raise ValueError(f"node {int(missing[0])} has no diagonal block in the pattern: its row is empty, the matrix singular")
+        if isinstance(preconditioner, str) and preconditioner == "multilevel":
+            preconditioner = MultilevelPreconditioner(K)
         self.K = K
         self.preconditioner = preconditioner
         self.rtol, self.atol, self.maxiter, self.check_every = float(rtol), float(atol), int(maxiter), int(check_every)
         self._op = _operator(K)
-        self._code = compile_kernels(K.gdim, preconditioner is not None)
+        #: the multilevel preconditioner, whose program holds the solver's kernels too (z and rz come from its cycle), or None
+        self._ml = preconditioner if isinstance(preconditioner, MultilevelPreconditioner) else None
+        self._code = self._ml._code if self._ml is not None else compile_kernels(K.gdim, preconditioner is not None)
         self.n = n
         self._work = {}  # device index -> (control, r, z, p, q, inv)
 
@@ -396,7 +415,7 @@ class ConjugateGradient:
             vectors = [torch.zeros(self.n, dtype=torch.float64, device=d) for _ in range(4 if self.preconditioner else 3)]
             if not self.preconditioner:
                 vectors.insert(1, vectors[0])  # z is r
-            inv = torch.zeros(self.K.gdim**2 * self.K.n_nodes if self.preconditioner else 2, dtype=torch.float64, device=d)
+            inv = torch.zeros(self.K.gdim**2 * self.K.n_nodes if self.preconditioner and self._ml is None else 2, dtype=torch.float64, device=d)
             w = self._work[dev] = (_Control(dev, self._op.nseg), *vectors, inv)
         return w
 
@@ -434,12 +453,18 @@ class ConjugateGradient:
             a.b, a.x, a.r, a.z, a.p, a.q, a.inv = (t.data_ptr() for t in (b, x, r, z, p, q, inv))
             a.has_x0 = 0 if x0 is None else 1
             cap = BLOCKS_PER_CU * jit.num_cu(dev)
-            if self.preconditioner:
+            ml = self._ml
+            if ml is not None:
+                ml._setup(dev, values, control)
+            elif self.preconditioner:
                 jit.launch(self._code, dev, max(1, min(-(-K.n_nodes // 256), cap)), a, "ConjugateGradient inverse launch", kernel=INVERSE_KERNEL)
             if x0 is not None:
                 op.apply(self._code, dev, a, x.data_ptr(), q.data_ptr(), _MODE_PLAIN)
             a.mode = _MODE_START
             jit.launch(self._code, dev, op.blocks(dev), a, "ConjugateGradient start launch", kernel=UPDATE_KERNEL)
+            if ml is not None:
+                ml._cycle(dev, values, control, r.data_ptr(), z.data_ptr())
+                ml._close(dev, control, r, z, p, start=True)
             direction_blocks = max(1, min(-(-n // 256), cap))
             control.download(dev)  # a solve that ends at its start (b = 0, a singular block, maxiter = 0) enqueues no iteration
             looks = 1
@@ -447,6 +472,9 @@ class ConjugateGradient:
                 for _ in range(self.check_every):
                     op.apply(self._code, dev, a, p.data_ptr(), q.data_ptr(), _MODE_ITERATE)
                     jit.launch(self._code, dev, op.blocks(dev), a, "ConjugateGradient update launch", kernel=UPDATE_KERNEL)
+                    if ml is not None:
+                        ml._cycle(dev, values, control, r.data_ptr(), z.data_ptr())
+                        ml._close(dev, control, r, z, p, start=False)
                     jit.launch(self._code, dev, direction_blocks, a, "ConjugateGradient direction launch", kernel=DIRECTION_KERNEL)
                 control.download(dev)
                 looks += 1

@@ -13,6 +13,7 @@ __path__ = [_os.path.join(_os.path.dirname(_os.path.dirname(_os.path.abspath(__f
 from ._api import *  # noqa: E402,F401,F403
 from ._api import __all__ as _api_all  # noqa: E402
 from ._api import __version__  # noqa: E402,F401
+from .multilevel import MultilevelPreconditioner  # noqa: E402,F401
 from .solver import ConjugateGradient  # noqa: E402,F401
 
-__all__ = [*_api_all, "ConjugateGradient"]
+__all__ = [*_api_all, "ConjugateGradient", "MultilevelPreconditioner"]
