@@ -60,6 +60,9 @@ CLOSE_KERNEL = "fcamd_ml_close_kernel"
 KERNELS = (GALERKIN_KERNEL, RESTRICT_KERNEL, PROLONG_KERNEL, SMOOTH_KERNEL, CLOSE_KERNEL)
 CYCLES = ("multiplicative", "additive")
 _MODE_QUIET = 3
+#: launch plans kept per device: one per (source, destination) pair of the applications in flight -- one in the conjugate
+#: gradients, two in BiCGStab (p -> y, s -> z), and the standalone ``apply`` beside them
+PLANS = 4
 
 __all__ = ["MultilevelPreconditioner", "aggregate", "coarsen", "compile_kernels", "hierarchy", "lds_bytes", "program"]
 
@@ -202,7 +205,7 @@ class _OnDevice:
             self.inv.append(zeros(dd * lv.n_nodes))
             self.q.append(zeros(d_ * lv.n_nodes))
         self.control = None  # of setup() and apply()
-        self.plan_key, self.plan, self.plan_holds = None, None, None
+        self.plans = {}  # key -> (launch plan, what it keeps alive), the last PLANS used
 
 
 class MultilevelPreconditioner:
@@ -429,9 +432,13 @@ class MultilevelPreconditioner:
         # that their addresses cannot be handed to other tensors while it is cached.
         key = (values.data_ptr(), control.device_block.data_ptr(), control.partials.data_ptr(), r_ptr, z_ptr, None if mask is None else mask.data_ptr(),
                tuple(t.data_ptr() for t in self._op.tables(dev)), jit.num_cu(dev))
-        if on.plan_key != key:
-            on.plan, on.plan_key, on.plan_holds = self._plan(dev, values, control, r_ptr, z_ptr), key, (control, mask)
-        for kernel, blocks, a, what in on.plan:
+        have = on.plans.pop(key, None)  # (taken out and put back: the dict keeps the order of the last use)
+        if have is None:
+            have = (self._plan(dev, values, control, r_ptr, z_ptr), (control, mask))
+            while len(on.plans) >= PLANS:
+                del on.plans[next(iter(on.plans))]
+        on.plans[key] = have
+        for kernel, blocks, a, what in have[0]:
             jit.launch(self._code, dev, blocks, a, what, kernel=kernel)
 
     def _close(self, dev: int, control, r, z, p, start: bool) -> None:

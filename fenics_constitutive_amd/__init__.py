@@ -13,7 +13,8 @@ __path__ = [_os.path.join(_os.path.dirname(_os.path.dirname(_os.path.abspath(__f
 from ._api import *  # noqa: E402,F401,F403
 from ._api import __all__ as _api_all  # noqa: E402
 from ._api import __version__  # noqa: E402,F401
+from .bicgstab import BiCGStab  # noqa: E402,F401
 from .multilevel import MultilevelPreconditioner  # noqa: E402,F401
 from .solver import ConjugateGradient  # noqa: E402,F401
 
-__all__ = [*_api_all, "ConjugateGradient", "MultilevelPreconditioner"]
+__all__ = [*_api_all, "BiCGStab", "ConjugateGradient", "MultilevelPreconditioner"]
