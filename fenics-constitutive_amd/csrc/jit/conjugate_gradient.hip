@@ -1,7 +1,7 @@
 // Preconditioned conjugate gradients on the assembled tangent stiffness (solver.py: ConjugateGradient): K x = b solved on the
 // device, K the values a TangentMatrix wrote (block CSR or scalar CSR over the same pattern).  Read at run time and compiled with
 // hiprtc behind the generated definitions:
-//   FCAMD_CG_D        dofs per node: 1, 2 or 3 (the blocks are D x D)
+//   FCAMD_CG_D        dofs per node: 1, 2 or 3 (the blocks are D x D); 6 for the rigid-body coarse levels of multilevel_rigid.hip
 //   FCAMD_CG_PRECOND  1: z = M^-1 r with the inverses of the nodes' own blocks (block-Jacobi); 0: z is r and rz is rr; 2: z and rz
 //                     come from outside (multilevel.hip: the cycle's kernels and its closing kernel run between the update and
 //                     the direction kernel); the update kernel forms neither
@@ -37,7 +37,10 @@
 // through LDS so that z[D v + r] = 0.0; z = z + inv[v][r][s] * r_[D v + s], s ascending, reads the node's other entries.  Its last
 // block ends the iteration: counts it, rr <= thr2 -> converged, a non-finite rr -> nonfinite, the count at maxiter -> maxiter.
 // Direction kernel: beta = rz / rz_old, p = z + beta * p.  Inverse kernel: the explicit inverses of the nodes' own blocks, once
-// per solve; a zero or non-finite determinant sets the status singular_block.  Dot kernel: the ordered dot of two vectors.
+// per solve; a zero or non-finite determinant sets the status singular_block.  D = 6: Gauss-Jordan in place, in registers, pivots
+// in the order 0 .. 5 without a search: p = m[k][k]; m[k][k] = 1.0; m[k][j] = m[k][j] / p, j ascending; then for the rows i != k
+// ascending: f = m[i][k]; m[i][k] = 0.0; m[i][j] = m[i][j] - f * m[k][j], j ascending; a zero or non-finite pivot sets
+// singular_block.  Dot kernel: the ordered dot of two vectors.
 // No floating-point atomics, no MFMA; every product is rounded before its sum (-ffp-contract=off); division is a division.
 #pragma once
 #include "tile_io.h"
@@ -54,7 +57,7 @@ constexpr int kSlab = FCAMD_CG_SLAB;
 constexpr int kChunks = kSlab / (2 * kWave);  // 16-byte loads of a lane per slab
 constexpr int kGrid = 6;                      // slabs start on multiples of 2 (16 bytes) and of D: a run of D values never straddles
 constexpr int kStep = kSlab / kGrid * kGrid;  // doubles of a slab that are used
-static_assert(D >= 1 && D <= 3 && kSeg % D == 0 && kSeg % kBlock == 0, "shape");
+static_assert(((D >= 1 && D <= 3) || D == 6) && kSeg % D == 0 && kSeg % kBlock == 0, "shape");
 static_assert(kSlab % (2 * kWave) == 0 && kSlab >= 2 * kWave, "slab");
 // solver.py (lds_bytes, LDS_CAP) refuses such a slab before it gets here
 static_assert((kWavesPerBlock * kSlab + kBlock + 2) * 8 <= 64 * 1024, "slab too large for the LDS of a block");
@@ -376,7 +379,29 @@ extern "C" __global__ void __launch_bounds__(fcamd::kBlock) fcamd_cg_inverse_ker
             for (int s = 0; s < D; ++s) m[r][s] = a.values[base + r * rstride + s];
         double* inv = a.inv + DD * v;
         double det;
-        if constexpr (D == 1) {
+        if constexpr (D == 6) {
+            det = 1.0;  // (stands for the pivots: 0.0 once one of them is zero or not finite)
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                const double p = m[k][k];
+                if (!(p != 0.0) || !__builtin_isfinite(p)) det = 0.0;
+                m[k][k] = 1.0;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) m[k][j] = m[k][j] / p;
+#pragma unroll
+                for (int i = 0; i < 6; ++i) {
+                    if (i == k) continue;
+                    const double f = m[i][k];
+                    m[i][k] = 0.0;
+#pragma unroll
+                    for (int j = 0; j < 6; ++j) m[i][j] = m[i][j] - f * m[k][j];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+#pragma unroll
+                for (int j = 0; j < 6; ++j) inv[6 * i + j] = m[i][j];
+        } else if constexpr (D == 1) {
             det = m[0][0];
             inv[0] = 1.0 / det;
         } else if constexpr (D == 2) {

@@ -38,6 +38,27 @@ not ``rz > 0``: status ``indefinite`` (the iteration has been counted).  Every k
 THE MULTIPLICATIVE CYCLE AND THE COARSEST SWEEPS NEED ``omega * lambda_max(D^-1 K) < 2``; nothing is refused for it and nothing
 estimates ``lambda_max``.  On the trilinear hexahedron cube it is 2.87, hence the default ``omega = 0.5``.
 
+*The rigid-body coarse space* (``coarse_space="rigid_body"``, ``coordinates``; csrc/jit/multilevel_rigid.hip).  Aggregation, coarse
+patterns, ``fold`` and ``members`` are the ones above; a coarse node carries ``Dc = D + R`` dofs, ``D`` translations and ``R``
+rotations (``R = 3`` in 3-D, ``1`` in 2-D; in 1-D there is no rotation and the translation hierarchy is built), so the blocks of the
+levels ``l >= 1`` are ``Dc x Dc``.  *Positions*: level 0 has ``coordinates``; a node of level ``l + 1`` has ``s = 0.0; s = s + x_i`` over the
+members ``i`` of its aggregate, ascending, then ``s / count`` (per coordinate).  *Offsets*: ``o_i = x_i - x_agg(i)``.  ``B(o)`` is the
+``D x R`` matrix of ``theta -> theta x o``: 3-D ``[[0, oz, -oy], [-oz, 0, ox], [oy, -ox, 0]]``, 2-D ``[-oy, ox]^T`` (a minus negates the
+offset's entry, the zeros are ``+0.0``).  The prolongation block of node ``i`` is ``P_i = [I_D  B(o_i)]`` (``D x Dc``) from level 0 and
+``P_i = [[I_D, B(o_i)], [0, I_R]]`` (``Dc x Dc``) from a level ``l >= 1``, formed in registers; all its entries take part in the sums,
+the zeros and ones too.  With ``Df`` the dofs per node of the fine level of a pair (``D`` or ``Dc``):
+*Galerkin values*, coarse block ``(I, J)``, entry ``(r, s)``: ``f = 0.0``; over the fine blocks ``k = (i, j)`` that fold into it, ascending:
+``t = 0.0``; for ``a`` ascending: ``u = 0.0; u = u + value_l(k, a, b) * P_j[b][s]``, ``b`` ascending; ``t = t + P_i[a][r] * u``; then
+``f = f + t``.  *Restriction*: ``rc[Dc I + c] = 0.0``; over the members ``i``, ascending: ``t = 0.0; t = t + P_i[a][c] * d[Df i + a]``, ``a``
+ascending; ``rc = rc + t``.  *Prolongation*: ``t = 0.0; t = t + P_i[r][c] * xc[Dc agg[i] + c]``, ``c`` ascending; ``x[Df i + r] = x[Df i + r] +
+t``, on level 0 skipped at the constrained dofs.  *Block inverses* of ``6 x 6`` blocks: Gauss-Jordan in place, pivots in the order
+0 .. 5 without a search: ``p = m[k][k]; m[k][k] = 1.0; m[k][j] = m[k][j] / p``, ``j`` ascending; for the rows ``i != k`` ascending:
+``f = m[i][k]; m[i][k] = 0.0; m[i][j] = m[i][j] - f * m[k][j]``, ``j`` ascending; a zero or non-finite pivot: ``singular_block``
+(``3 x 3`` blocks, 2-D: the solver's cofactor formulas).  Smoothing, products and cycles are the ones above on the levels' own block
+sizes.  Two programs per object: the fine one (``FCAMD_CG_D = D``, the object's ``_code``, with the ``(D, Dc)`` transfer kernels) and the
+coarse one (``FCAMD_CG_D = Dc``: every level ``l >= 1`` and the ``(Dc, Dc)`` transfer kernels).  A level-0 aggregate whose columns of ``P``
+are linearly dependent -- a lone node, all members at one point, in 3-D all members on one line -- is refused at construction.
+
 LDS of a block: ``lds_bytes(kernel)``.
 """
 
@@ -58,20 +79,28 @@ PROLONG_KERNEL = "fcamd_ml_prolong_kernel"
 SMOOTH_KERNEL = "fcamd_ml_smooth_kernel"
 CLOSE_KERNEL = "fcamd_ml_close_kernel"
 KERNELS = (GALERKIN_KERNEL, RESTRICT_KERNEL, PROLONG_KERNEL, SMOOTH_KERNEL, CLOSE_KERNEL)
+RIGID_GALERKIN_KERNEL = "fcamd_mr_galerkin_kernel"
+RIGID_RESTRICT_KERNEL = "fcamd_mr_restrict_kernel"
+RIGID_PROLONG_KERNEL = "fcamd_mr_prolong_kernel"
+RIGID_KERNELS = (RIGID_GALERKIN_KERNEL, RIGID_RESTRICT_KERNEL, RIGID_PROLONG_KERNEL)
 CYCLES = ("multiplicative", "additive")
+COARSE_SPACES = ("translations", "rigid_body")
 _MODE_QUIET = 3
 #: launch plans kept per device: one per (source, destination) pair of the applications in flight -- one in the conjugate
 #: gradients, two in BiCGStab (p -> y, s -> z), and the standalone ``apply`` beside them
 PLANS = 4
 
-__all__ = ["MultilevelPreconditioner", "aggregate", "coarsen", "compile_kernels", "hierarchy", "lds_bytes", "program"]
+__all__ = ["MultilevelPreconditioner", "aggregate", "coarse_dofs", "coarsen", "compile_kernels", "compile_rigid_kernels", "hierarchy", "lds_bytes",
+           "place", "program", "rigid_program"]
 
 
 def lds_bytes(kernel: str = CLOSE_KERNEL) -> int:
-    """LDS of one block of ``kernel``: the tree of the dot and the last-block flag in the closing kernel, nothing in the other four;
-    the solver's kernels of the same program: ``solver.lds_bytes(kernel, False)``"""
+    """LDS of one block of ``kernel``: the tree of the dot and the last-block flag in the closing kernel, nothing in the other four
+    nor in the three of the rigid-body coarse space; the solver's kernels of the same program: ``solver.lds_bytes(kernel, False)``"""
     if kernel in solver.KERNELS:
         return solver.lds_bytes(kernel, False)
+    if kernel in RIGID_KERNELS:
+        return 0
     return {CLOSE_KERNEL: 8 * (256 + 2), GALERKIN_KERNEL: 0, RESTRICT_KERNEL: 0, PROLONG_KERNEL: 0, SMOOTH_KERNEL: 0}[kernel]
 
 
@@ -90,6 +119,35 @@ def compile_kernels(gdim: int):
         if scratch:
             raise ValueError(f"multilevel_{gdim}d: {kernel} compiles with {scratch} bytes of scratch per lane")
     return code
+
+
+def coarse_dofs(gdim: int) -> int:
+    """``Dc``: the dofs of a coarse node of the rigid-body coarse space, translations and rotations (1-D: no rotation)"""
+    return {1: 1, 2: 3, 3: 6}[int(gdim)]
+
+
+def rigid_program(gdim: int, block: int, slab: int = solver.SLAB) -> str:
+    """the program text of the rigid-body coarse space in ``gdim`` dimensions with blocks of ``block`` dofs per node: ``gdim`` (the
+    fine program) or ``coarse_dofs(gdim)`` (the coarse program)"""
+    return "\n".join([f"#define FCAMD_CG_D {int(block)}", "#define FCAMD_CG_PRECOND 2", f"#define FCAMD_CG_SLAB {int(slab)}",
+                      f"#define FCAMD_ML_GDIM {int(gdim)}", '#include "multilevel_rigid.hip"']) + "\n"
+
+
+def compile_rigid_kernels(gdim: int):
+    """``(fine, coarse)``: the two code objects of the rigid-body coarse space in 2 or 3 dimensions, thirteen kernels in each (no GPU
+    needed).  A kernel with scratch is a ``ValueError``."""
+    if gdim not in (2, 3):
+        raise ValueError(f"the rigid-body coarse space is for 2 or 3 dofs per node, got {gdim}")
+    codes = []
+    for block in (gdim, coarse_dofs(gdim)):
+        name = f"multilevel_rigid_{gdim}d_{block}"
+        code = jit.compile_program(rigid_program(gdim, block), name, solver.MATVEC_KERNEL)
+        for kernel in solver.KERNELS + KERNELS + RIGID_KERNELS:
+            scratch = kernel_resources(code.log, kernel)["scratch_bytes"]
+            if scratch:
+                raise ValueError(f"{name}: {kernel} compiles with {scratch} bytes of scratch per lane")
+        codes.append(code)
+    return tuple(codes)
 
 
 # ---- the hierarchy (host) --------------------------------------------------------------------------------------------------------
@@ -144,7 +202,9 @@ class Level:
         self.diag_block = np.full(self.n_nodes, -1, dtype=np.int64)
         on = np.flatnonzero(indices == rows)
         self.diag_block[rows[on]] = on
+        self.block_row = rows  # the row node of every block
         self.agg = self.roots = self.mem_ptr = self.members = self.fold_ptr = self.fold = None
+        self.position = self.offset = None  # place(): [n_nodes][gdim] each; the coarsest level has no offset
 
 
 def hierarchy(indptr: np.ndarray, indices: np.ndarray, coarsest_nodes: int = 64, max_levels: int = 10) -> list:
@@ -165,6 +225,38 @@ def hierarchy(indptr: np.ndarray, indices: np.ndarray, coarsest_nodes: int = 64,
     return levels
 
 
+def place(levels: list, coordinates: np.ndarray) -> None:
+    """the position of every node of every level and its offset from its aggregate's position (module docstring): level 0 has
+    ``coordinates``, a coarse node the sum of its members' positions, ascending, divided by their count"""
+    levels[0].position = np.ascontiguousarray(coordinates, dtype=np.float64)
+    for fine, coarse in zip(levels[:-1], levels[1:]):
+        total = np.zeros((coarse.n_nodes, fine.position.shape[1]))
+        np.add.at(total, fine.agg, fine.position)  # unbuffered, in the order of the nodes: ascending within an aggregate
+        coarse.position = total / np.diff(fine.mem_ptr).astype(np.float64)[:, None]
+        fine.offset = fine.position - coarse.position[fine.agg]
+
+
+def _refuse_degenerate(lv) -> None:
+    """a level-0 aggregate whose columns of ``P`` are linearly dependent: a ``ValueError`` that names it"""
+    g = lv.offset.shape[1]
+    for a in range(lv.roots.size):
+        mine = lv.members[lv.mem_ptr[a]: lv.mem_ptr[a + 1]]
+        sv = np.linalg.svd(lv.offset[mine], compute_uv=False)
+        rank = int((sv > 1e-10 * sv[0]).sum()) if sv[0] > 0.0 else 0
+        if rank >= g - 1:
+            continue
+        what = "is a lone node" if mine.size == 1 else "has all its members at one point" if rank == 0 else "has all its members on one line"
+        raise ValueError(f"aggregate {a} of level 0 (root {int(lv.roots[a])}, {mine.size} members) {what}: its rigid-body modes are linearly dependent")
+
+
+class RigidArgs(C.Structure):
+    """ctypes mirror of fcamd_mr::Args (multilevel_rigid.hip)"""
+
+    _fields_ = [(name, C.c_void_p) for name in ("fine_values", "coarse_values", "fold_ptr", "fold", "dest_base", "dest_stride", "block_row", "indices",
+                                                "offsets", "mem_ptr", "members", "agg", "mask", "b", "q", "x", "xc", "rc", "sc")] + \
+               [("n", C.c_int64), ("n_coarse", C.c_int64), ("use_q", C.c_int32), ("pad", C.c_int32)]
+
+
 class Args(C.Structure):
     """ctypes mirror of fcamd_ml::Args (multilevel.hip)"""
 
@@ -183,7 +275,7 @@ class _OnDevice:
         from .hostio import to_device
 
         d = torch.device("cuda", dev)
-        dd, d_ = pc.K.gdim**2, pc.K.gdim
+        dofs = pc._dofs  # per node, by level
 
         def zeros(n):
             return torch.zeros(max(int(n), 2), dtype=torch.float64, device=d)
@@ -195,15 +287,16 @@ class _OnDevice:
             if l > 0:
                 t["indptr"], t["indices"] = to_device(lv.indptr, d), to_device(lv.indices, d)
                 t["diag"] = to_device(np.maximum(lv.diag_block, 0).astype(np.int32), d)
-                self.values.append(zeros(dd * lv.nnzb))
-                self.b.append(zeros(d_ * lv.n_nodes))
-                self.x.append(zeros(d_ * lv.n_nodes))
+                self.values.append(zeros(dofs[l]**2 * lv.nnzb))
+                self.b.append(zeros(dofs[l] * lv.n_nodes))
+                self.x.append(zeros(dofs[l] * lv.n_nodes))
             if lv.agg is not None:
-                for name in ("agg", "mem_ptr", "members", "fold_ptr", "fold"):
-                    t[name] = to_device(getattr(lv, name), d)
+                for name in ("agg", "mem_ptr", "members", "fold_ptr", "fold") + (("block_row", "indices", "offset") if pc._rigid else ()):
+                    if name not in t:  # (a coarse level's column nodes are there already)
+                        t[name] = to_device(getattr(lv, name), d)
             self.tables.append(t)
-            self.inv.append(zeros(dd * lv.n_nodes))
-            self.q.append(zeros(d_ * lv.n_nodes))
+            self.inv.append(zeros(dofs[l]**2 * lv.n_nodes))
+            self.q.append(zeros(dofs[l] * lv.n_nodes))
         self.control = None  # of setup() and apply()
         self.plans = {}  # key -> (launch plan, what it keeps alive), the last PLANS used
 
@@ -220,14 +313,37 @@ class MultilevelPreconditioner:
     solve.  Built on the host at construction from the pattern alone, with the kernels compiled there (no GPU needed); a level
     with a node without a diagonal block is refused.  ``levels``, ``aggregates(l)``, ``pattern(l)``, ``members(l)``, ``folds(l)`` and
     ``roots(l)`` show the tables.  All value and vector tensors of the hierarchy belong to the object, one set per device,
-    allocated at the first call; use an object from one stream at a time."""
+    allocated at the first call; use an object from one stream at a time.
+
+    ``coarse_space``: "translations" (the default: ``D x D`` coarse blocks, an aggregate moves as a whole) or "rigid_body" with
+    ``coordinates``, the float64 array ``[K.n_nodes][K.gdim]`` of the positions of the pattern's nodes: an aggregate rotates too, the
+    nodes of the levels ``l >= 1`` carry ``coarse_dofs`` = 6 (3-D) or 3 (2-D) dofs (module docstring; 1-D: the translation
+    hierarchy).  A level-0 aggregate whose rigid-body modes are linearly dependent -- a lone node, all members at one point, in 3-D
+    all on one line -- is a ``ValueError`` that names it, raised before anything is compiled.  ``positions(l)`` and ``offsets(l)``
+    show where the nodes were placed."""
 
     def __init__(self, K: TangentMatrix, cycle: str = "multiplicative", smoothing: int = 1, omega: float = 0.5, coarsest_nodes: int = 64,
-                 coarsest_sweeps: int = 8, max_levels: int = 10):
+                 coarsest_sweeps: int = 8, max_levels: int = 10, coarse_space: str = "translations", coordinates=None):
         if not isinstance(K, TangentMatrix):
             raise TypeError(f"K must be a TangentMatrix, got {type(K).__name__}")
         if cycle not in CYCLES:
             raise ValueError(f"cycle must be one of {CYCLES}, got {cycle!r}")
+        if not (isinstance(coarse_space, str) and coarse_space in COARSE_SPACES):
+            raise ValueError(f"coarse_space must be one of {COARSE_SPACES}, got {coarse_space!r}")
+        if coarse_space == "translations":
+            if coordinates is not None:
+                raise ValueError('coordinates belong to coarse_space="rigid_body"; the translations need none')
+        else:
+            if coordinates is None:
+                raise ValueError('coarse_space="rigid_body" needs coordinates, the positions [n_nodes][gdim] of the nodes of the pattern')
+            if not isinstance(coordinates, np.ndarray):
+                raise TypeError(f"coordinates must be a NumPy array, got {type(coordinates).__name__}")
+            if coordinates.dtype != np.float64:
+                raise TypeError(f"coordinates must be float64, got {coordinates.dtype}")
+            if coordinates.shape != (K.n_nodes, K.gdim):
+                raise ValueError(f"coordinates must have the shape {(K.n_nodes, K.gdim)}, got {coordinates.shape}")
+            if not np.isfinite(coordinates).all():
+                raise ValueError("coordinates must be finite")
         if isinstance(omega, bool) or not isinstance(omega, (int, float, np.integer, np.floating)):
             raise TypeError(f"omega must be a number, got {type(omega).__name__}")
         if not (omega > 0.0 and np.isfinite(omega)):
@@ -249,8 +365,20 @@ class MultilevelPreconditioner:
             missing = np.flatnonzero(lv.diag_block < 0)
             if missing.size:
                 raise ValueError(f"node {int(missing[0])} of level {l} has no diagonal block in the pattern")
+        self._coarse_space = coarse_space
+        #: the coarse nodes carry rotations (in 1-D there is none: the translation hierarchy, its program and its bits)
+        self._rigid = coarse_space == "rigid_body" and K.gdim > 1
+        if coordinates is not None:
+            place(self._levels, coordinates)
+            if self._rigid and len(self._levels) > 1:
+                _refuse_degenerate(self._levels[0])
+        #: dofs per node, by level
+        self._dofs = [K.gdim] + [coarse_dofs(K.gdim) if self._rigid else K.gdim] * (len(self._levels) - 1)
         self._op = solver._operator(K)
-        self._code = compile_kernels(K.gdim)
+        if self._rigid:
+            self._code, self._coarse_code = compile_rigid_kernels(K.gdim)
+        else:
+            self._code = self._coarse_code = compile_kernels(K.gdim)
         self._on = {}  # device index -> _OnDevice
 
     # ---- what was asked for (read-only) ----------------------------------------------------------------------------------------
@@ -260,6 +388,7 @@ class MultilevelPreconditioner:
     coarsest_nodes = property(lambda self: self._coarsest_nodes)
     coarsest_sweeps = property(lambda self: self._coarsest_sweeps)
     max_levels = property(lambda self: self._max_levels)
+    coarse_space = property(lambda self: self._coarse_space)
 
     # ---- what was built --------------------------------------------------------------------------------------------------------
     @property
@@ -299,13 +428,40 @@ class MultilevelPreconditioner:
         return self._levels[l].diag_block
 
     @property
+    def coarse_dofs(self) -> int:
+        """``Dc``: the dofs of a node of the levels ``l >= 1`` (``D`` with the translations)"""
+        return coarse_dofs(self.K.gdim) if self._rigid else self.K.gdim
+
+    def positions(self, l: int) -> np.ndarray:
+        """``[nodes][D]``: the position of every node of level ``l`` (``coarse_space="rigid_body"``)"""
+        self.pattern(l)
+        if self._levels[l].position is None:
+            raise ValueError('only coarse_space="rigid_body" places the nodes')
+        return self._levels[l].position
+
+    def offsets(self, l: int) -> np.ndarray:
+        """``[nodes][D]``: the offset of every node of level ``l`` from the position of its aggregate (``coarse_space="rigid_body"``)"""
+        if self._fine(l).offset is None:
+            raise ValueError('only coarse_space="rigid_body" places the nodes')
+        return self._fine(l).offset
+
+    @property
     def resources(self) -> dict:
         """the compiler's remarks of the five multilevel kernels, by "galerkin", "restrict", "prolong", "smooth" and "close" """
-        return {kernel[len("fcamd_ml_"): -len("_kernel")]: kernel_resources(self._code.log, kernel) for kernel in KERNELS}
+        r = {kernel[len("fcamd_ml_"): -len("_kernel")]: kernel_resources(self._code.log, kernel) for kernel in KERNELS}
+        if self._rigid:  # the three transfer kernels of the pair (D, Dc), and under "coarse" every kernel of the coarse program by its name
+            r.update({"rigid_" + kernel[len("fcamd_mr_"): -len("_kernel")]: kernel_resources(self._code.log, kernel) for kernel in RIGID_KERNELS})
+            r["coarse"] = {kernel: kernel_resources(self._coarse_code.log, kernel) for kernel in solver.KERNELS + KERNELS + RIGID_KERNELS}
+        return r
 
     @property
     def compile_log(self) -> str:
         return self._code.log
+
+    @property
+    def coarse_compile_log(self) -> str:
+        """the log of the program of the levels ``l >= 1`` (with the translations: the one program there is)"""
+        return self._coarse_code.log
 
     @staticmethod
     def lds_bytes(kernel: str = CLOSE_KERNEL) -> int:
@@ -331,7 +487,7 @@ class MultilevelPreconditioner:
             a = self._op.args(dev, values, control)
         else:
             on, lv, t = self._device(dev), self._levels[l], self._device(dev).tables[l]
-            d_ = self.K.gdim
+            d_ = self._dofs[l]
             a = solver.Args()
             a.values, a.indptr, a.indices, a.diag, a.groups = (on.values[l].data_ptr(), t["indptr"].data_ptr(), t["indices"].data_ptr(), t["diag"].data_ptr(),
                                                                on.dummy.data_ptr())
@@ -339,6 +495,10 @@ class MultilevelPreconditioner:
             a.n, a.nnz, a.nseg, a.n_nodes, a.csr = d_ * lv.n_nodes, d_ * d_ * lv.nnzb, solver._segments(d_ * lv.n_nodes), lv.n_nodes, 0
         a.inv = self._device(dev).inv[l].data_ptr()
         return a
+
+    def _program(self, l: int):
+        """the code object of level ``l``'s own kernels and of the transfers between it and level ``l + 1``"""
+        return self._code if l == 0 else self._coarse_code
 
     @staticmethod
     def _blocks(n: int, cap: int) -> int:
@@ -349,6 +509,17 @@ class MultilevelPreconditioner:
         on, cap, dd = self._device(dev), BLOCKS_PER_CU * jit.num_cu(dev), self.K.gdim**2
         tables = self.K._tables(dev)
         for l, lv in enumerate(self._levels[:-1]):
+            if self._rigid:
+                a, t = RigidArgs(), on.tables[l]
+                a.fine_values = (values if l == 0 else on.values[l]).data_ptr()
+                a.coarse_values = on.values[l + 1].data_ptr()
+                a.fold_ptr, a.fold, a.block_row, a.indices, a.offsets = (t[name].data_ptr() for name in ("fold_ptr", "fold", "block_row", "indices", "offset"))
+                if l == 0:
+                    a.dest_base, a.dest_stride = tables[2].data_ptr(), tables[3].data_ptr()
+                a.sc = control.device_block.data_ptr()
+                a.n_coarse = self._dofs[l + 1]**2 * self._levels[l + 1].nnzb
+                jit.launch(self._program(l), dev, self._blocks(a.n_coarse, cap), a, "MultilevelPreconditioner rigid-body Galerkin launch", kernel=RIGID_GALERKIN_KERNEL)
+                continue
             a = Args()
             a.fine_values = (values if l == 0 else on.values[l]).data_ptr()
             a.coarse_values = on.values[l + 1].data_ptr()
@@ -359,15 +530,15 @@ class MultilevelPreconditioner:
             a.n_coarse = dd * self._levels[l + 1].nnzb
             jit.launch(self._code, dev, self._blocks(a.n_coarse, cap), a, "MultilevelPreconditioner Galerkin launch", kernel=GALERKIN_KERNEL)
         for l, lv in enumerate(self._levels):
-            jit.launch(self._code, dev, self._blocks(lv.n_nodes, cap), self._level_args(dev, l, values, control), "MultilevelPreconditioner inverse launch",
+            jit.launch(self._program(l), dev, self._blocks(lv.n_nodes, cap), self._level_args(dev, l, values, control), "MultilevelPreconditioner inverse launch",
                        kernel=solver.INVERSE_KERNEL)
 
     def _plan(self, dev: int, values, control, r_ptr: int, z_ptr: int) -> list:
-        """the launches of one application ``z = M^-1 r``: ``[(kernel, blocks, args, what)]``"""
-        on, cap, d_ = self._device(dev), BLOCKS_PER_CU * jit.num_cu(dev), self.K.gdim
+        """the launches of one application ``z = M^-1 r``: ``[(code, kernel, blocks, args, what)]``"""
+        on, cap = self._device(dev), BLOCKS_PER_CU * jit.num_cu(dev)
         mask = self.K._mask_table(dev)
         sc = control.device_block.data_ptr()
-        n_of = [d_ * lv.n_nodes for lv in self._levels]
+        n_of = [d_ * lv.n_nodes for d_, lv in zip(self._dofs, self._levels)]
         b_of = [r_ptr] + [t.data_ptr() for t in on.b[1:]]
         x_of = [z_ptr] + [t.data_ptr() for t in on.x[1:]]
         q_of = [t.data_ptr() for t in on.q]
@@ -377,13 +548,13 @@ class MultilevelPreconditioner:
         def product(l):
             a = self._level_args(dev, l, values, control)
             a.va, a.q, a.mode = x_of[l], q_of[l], _MODE_QUIET
-            ops.append((solver.MATVEC_KERNEL, max(1, min(int(a.nseg), cap)), a, "MultilevelPreconditioner matrix-vector launch"))
+            ops.append((self._program(l), solver.MATVEC_KERNEL, max(1, min(int(a.nseg), cap)), a, "MultilevelPreconditioner matrix-vector launch"))
 
         def smooth(l, first=0, plain=0, use_q=0):
             a = Args()
             a.b, a.q, a.x, a.inv, a.sc, a.omega, a.n = b_of[l], q_of[l], x_of[l], on.inv[l].data_ptr(), sc, self.omega, n_of[l]
             a.first, a.plain, a.use_q = first, plain, use_q
-            ops.append((SMOOTH_KERNEL, self._blocks(n_of[l], cap), a, "MultilevelPreconditioner smoothing launch"))
+            ops.append((self._program(l), SMOOTH_KERNEL, self._blocks(n_of[l], cap), a, "MultilevelPreconditioner smoothing launch"))
 
         def sweeps(l, count, from_zero):
             for i in range(count):
@@ -394,16 +565,22 @@ class MultilevelPreconditioner:
                     smooth(l, use_q=1)
 
         def restrict(l, use_q):
-            a, t = Args(), on.tables[l]
+            a, t = (RigidArgs() if self._rigid else Args()), on.tables[l]
+            if self._rigid:
+                a.offsets = t["offset"].data_ptr()
             a.mem_ptr, a.members, a.b, a.q, a.rc, a.sc, a.n_coarse, a.use_q = t["mem_ptr"].data_ptr(), t["members"].data_ptr(), b_of[l], q_of[l], b_of[l + 1], sc, n_of[l + 1], use_q
-            ops.append((RESTRICT_KERNEL, self._blocks(n_of[l + 1], cap), a, "MultilevelPreconditioner restriction launch"))
+            ops.append((self._program(l), RIGID_RESTRICT_KERNEL if self._rigid else RESTRICT_KERNEL, self._blocks(n_of[l + 1], cap), a,
+                        "MultilevelPreconditioner restriction launch"))
 
         def prolong(l):
-            a = Args()
+            a = RigidArgs() if self._rigid else Args()
+            if self._rigid:
+                a.offsets = on.tables[l]["offset"].data_ptr()
             a.agg, a.x, a.xc, a.sc, a.n = on.tables[l]["agg"].data_ptr(), x_of[l], x_of[l + 1], sc, n_of[l]
             if l == 0 and mask is not None:
                 a.mask = mask.data_ptr()
-            ops.append((PROLONG_KERNEL, self._blocks(n_of[l], cap), a, "MultilevelPreconditioner prolongation launch"))
+            ops.append((self._program(l), RIGID_PROLONG_KERNEL if self._rigid else PROLONG_KERNEL, self._blocks(n_of[l], cap), a,
+                        "MultilevelPreconditioner prolongation launch"))
 
         if self.cycle == "additive":
             for l in range(last):
@@ -431,15 +608,15 @@ class MultilevelPreconditioner:
         # partial sums, the vectors, the mask and the level-0 tables.  The control and the mask are kept alive with the plan, so
         # that their addresses cannot be handed to other tensors while it is cached.
         key = (values.data_ptr(), control.device_block.data_ptr(), control.partials.data_ptr(), r_ptr, z_ptr, None if mask is None else mask.data_ptr(),
-               tuple(t.data_ptr() for t in self._op.tables(dev)), jit.num_cu(dev))
+               tuple(t.data_ptr() for t in self._op.tables(dev)), jit.num_cu(dev), self._coarse_space)
         have = on.plans.pop(key, None)  # (taken out and put back: the dict keeps the order of the last use)
         if have is None:
             have = (self._plan(dev, values, control, r_ptr, z_ptr), (control, mask))
             while len(on.plans) >= PLANS:
                 del on.plans[next(iter(on.plans))]
         on.plans[key] = have
-        for kernel, blocks, a, what in have[0]:
-            jit.launch(self._code, dev, blocks, a, what, kernel=kernel)
+        for code, kernel, blocks, a, what in have[0]:
+            jit.launch(code, dev, blocks, a, what, kernel=kernel)
 
     def _close(self, dev: int, control, r, z, p, start: bool) -> None:
         """the closing kernel behind a cycle: ``rz``, ``rz_old``, in the start ``p = z``"""
@@ -457,7 +634,7 @@ class MultilevelPreconditioner:
 
     # ---- standalone --------------------------------------------------------------------------------------------------------------
     def setup(self, values) -> list:
-        """The value tensors of the coarse levels (block CSR, ``[blocks][D][D]`` flat), finest first, formed from ``values`` with the
+        """The value tensors of the coarse levels (block CSR, ``[blocks][D][D]`` flat; ``[blocks][Dc][Dc]`` with the rigid-body modes), finest first, formed from ``values`` with the
         inverses of every level (asynchronous, on torch's current stream).  The tensors are the object's own: the next call writes
         them again."""
         import torch
@@ -468,7 +645,7 @@ class MultilevelPreconditioner:
             if self.K.shape[0]:
                 self._setup(dev, values, self._own_control(dev))
             on = self._device(dev)
-            return [on.values[l][: self.K.gdim**2 * lv.nnzb] for l, lv in enumerate(self._levels) if l > 0]
+            return [on.values[l][: self._dofs[l]**2 * lv.nnzb] for l, lv in enumerate(self._levels) if l > 0]
 
     def apply(self, values, r, out=None):
         """``out = M^-1 r`` for the matrix ``values`` (asynchronous, on torch's current stream); ``out`` must not alias ``r``.  With a
