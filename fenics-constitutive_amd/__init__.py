@@ -6,5 +6,6 @@ from ._api import __version__  # noqa: F401
 from .bicgstab import BiCGStab  # noqa: F401
 from .multilevel import MultilevelPreconditioner  # noqa: F401
 from .solver import ConjugateGradient  # noqa: F401
+from .tangent_operator import TangentOperator  # noqa: F401
 
-__all__ = [*_api_all, "BiCGStab", "ConjugateGradient", "MultilevelPreconditioner"]
+__all__ = [*_api_all, "BiCGStab", "ConjugateGradient", "MultilevelPreconditioner", "TangentOperator"]

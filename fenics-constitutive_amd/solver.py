@@ -48,6 +48,13 @@ the result is the same bits for every ``check_every``.  No cooperative launch, n
 follow it in every iteration and in the start, and the coarse levels' products run in the matrix-vector kernel's mode 3, which
 honours the status and touches neither ``pq`` nor the counter.
 
+*Without a matrix.*  ``ConjugateGradient(A)`` with a ``TangentOperator`` (tangent_operator.py) solves the same system from the
+tangent of the quadrature points: ``cg(tangent, b, x0=None, out=None)``.  The product and ``p . q`` come from the operator's two kernels
+through the same seam (``_FreeOperator`` in ``_Operator``'s place; the same control block, modes and ordered dot), block-Jacobi from the
+operator's diagonal-block kernels followed by THIS module's inverse kernel on the block array -- a BSR values array whose diagonal
+table is ``0 .. n-1`` --, and the start, update and direction kernels are used as they are.  The multilevel preconditioner needs the
+matrix and is refused.
+
 LDS of a block: ``lds_bytes(kernel)``; the same ``LDS_CAP`` as the other operators.
 """
 
@@ -62,6 +69,8 @@ from . import jit
 from .force import kernel_resources
 from .gradient import BLOCKS_PER_CU, LDS_CAP
 from .matrix import TangentMatrix
+from .tangent_operator import MODE_QUIET as _MODE_QUIET
+from .tangent_operator import TangentOperator
 
 MATVEC_KERNEL = "fcamd_cg_matvec_kernel"
 UPDATE_KERNEL = "fcamd_cg_update_kernel"
@@ -235,6 +244,49 @@ class _Operator:
         jit.launch(code, dev, self.blocks(dev), a, "ConjugateGradient matrix-vector launch", kernel=MATVEC_KERNEL)
 
 
+class _FreeOperator:
+    """The seam for a ``TangentOperator``: ``q = A p`` with ``p . q`` behind it by the operator's own two kernels, from the tangent of
+    the quadrature points (``values`` is that tangent here).  The block array the inverse kernel reads is a BSR values array whose
+    pattern is the diagonal: ``indptr`` and the diagonal table are both ``0 .. n``, one table on the device."""
+
+    def __init__(self, operator: TangentOperator):
+        self.matrix, self.gdim = operator, operator.gdim
+        self.n, self.nnz, self.n_nodes = operator.shape[0], 0, operator.n_nodes
+        self.nseg = _segments(self.n)
+        self.csr = 0
+        self._on = {}  # device index -> (0 .. n_nodes as int32,)
+        self._control = {}  # device index -> _Control (of the plain product)
+
+    def tables(self, dev: int):
+        t = self._on.get(dev)
+        if t is None:
+            import torch
+
+            from .hostio import to_device
+
+            d = torch.device("cuda", dev)
+            with torch.cuda.device(d):
+                t = self._on[dev] = (to_device(np.arange(self.n_nodes + 1, dtype=np.int32), d),)
+        return t
+
+    def args(self, dev: int, tangent, control: _Control) -> Args:
+        (count,) = self.tables(dev)
+        a = Args()
+        a.indptr = a.indices = a.diag = a.groups = count.data_ptr()
+        a.partials, a.sc = control.partials.data_ptr(), control.device_block.data_ptr()
+        a.n, a.nnz, a.nseg, a.n_nodes, a.csr = self.n, self.gdim * self.gdim * self.n_nodes, self.nseg, self.n_nodes, 0
+        a.values = tangent.data_ptr()  # (the inverse kernel is launched with the block array in its place)
+        return a
+
+    def blocks(self, dev: int) -> int:
+        return max(1, min(self.nseg, BLOCKS_PER_CU * jit.num_cu(dev)))
+
+    def apply(self, code, dev: int, a: Args, vector_ptr: int, out_ptr: int, mode: int) -> None:
+        """``out = A vector`` and the ordered ``vector . out`` by the operator's kernels (``code``, the solver's program, is not used)"""
+        a.va, a.q, a.mode = vector_ptr, out_ptr, mode  # (as _Operator.apply leaves them: the update kernel reads the mode)
+        self.matrix._apply(dev, a.values, vector_ptr, out_ptr, mode, a.partials, a.sc)
+
+
 _dot_control: dict = {}  # device index -> (_Control, segments it holds)
 
 
@@ -252,7 +304,7 @@ def _operator(matrix: TangentMatrix) -> _Operator:
     """the operator of ``matrix``, made at the first use and kept on the matrix object: it lives and dies with it"""
     op = getattr(matrix, "_solver_operator", None)
     if op is None:
-        op = matrix._solver_operator = _Operator(matrix)
+        op = matrix._solver_operator = _FreeOperator(matrix) if isinstance(matrix, TangentOperator) else _Operator(matrix)
     return op
 
 
@@ -261,6 +313,8 @@ def matvec(K: TangentMatrix, values, p, out=None):
     wrote, ``p`` and ``out`` float64 device tensors of ``D n_nodes`` entries.  A row without blocks is ``+0.0``."""
     import torch
 
+    if isinstance(K, TangentOperator):
+        return _free_matvec(K, values, p, out)
     if not isinstance(K, TangentMatrix):
         raise TypeError(f"K must be a TangentMatrix, got {type(K).__name__}")
     dev = K.device
@@ -281,6 +335,30 @@ def matvec(K: TangentMatrix, values, p, out=None):
         if control is None:
             control = op._control[dev] = _Control(dev, op.nseg)
         op.apply(_plain_code(K.gdim), dev, op.args(dev, values, control), p.data_ptr(), out.data_ptr(), _MODE_PLAIN)
+    return out
+
+
+def _free_matvec(A: TangentOperator, tangent, p, out=None):
+    """``matvec`` for a ``TangentOperator``: ``out = A p`` from ``tangent`` in ``_MODE_PLAIN`` -- the ordered ``p . out`` is left in the ``dot``
+    of the control block the operator's seam keeps (asynchronous, on torch's current stream)"""
+    import torch
+
+    dev = A.device
+    n = A.shape[0]
+    A._check("tangent", tangent, A.tangent_dim * A.n_points, dev)
+    A._check("p", p, n, dev)
+    if out is not None:
+        A._check("out", out, n, dev)
+        if _overlap(out, p):
+            raise ValueError("out must not alias p")
+    op = _operator(A)
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=torch.device("cuda", dev))
+        control = op._control.get(dev)
+        if control is None:
+            control = op._control[dev] = _Control(dev, op.nseg)
+        op.apply(None, dev, op.args(dev, tangent, control), p.data_ptr(), out.data_ptr(), _MODE_PLAIN)
     return out
 
 
@@ -344,14 +422,23 @@ class ConjugateGradient:
     which a node has no diagonal block -- an empty row, a singular matrix -- is refused there.  Work vectors, the inverse blocks,
     the partial sums and the control block belong to the object, one set per device, allocated at the first call.  All launches
     go to torch's current stream; THE CALL IS SYNCHRONOUS AT ITS END (and at every look before): it reads the final status, count
-    and norms back, so the stream has been waited for when it returns.  Use an object from one stream at a time."""
+    and norms back, so the stream has been waited for when it returns.  Use an object from one stream at a time.
+
+    ``K`` may be a ``TangentOperator`` instead: the call is then ``cg(tangent, b, x0=None, out=None)`` with the ``S*S n_points`` tangent a law
+    wrote in the values' place, ``preconditioner`` is "block_jacobi" or ``None`` ("multilevel" or a ``MultilevelPreconditioner``: a
+    ``ValueError``, its Galerkin values need the matrix), and a node that belongs to no cell is refused at construction as a missing
+    diagonal block is.  Everything else -- ``x0``, ``check_every``, the statuses, ``SolveResult`` and its ``looks`` -- is the same."""
 
     def __init__(self, K: TangentMatrix, preconditioner="block_jacobi", rtol: float = 1e-8, atol: float = 0.0, maxiter: int | None = None,
                  check_every: int = 16):
-        if not isinstance(K, TangentMatrix):
+        free = isinstance(K, TangentOperator)
+        if not free and not isinstance(K, TangentMatrix):
             raise TypeError(f"K must be a TangentMatrix, got {type(K).__name__}")
         from .multilevel import MultilevelPreconditioner
 
+        if free and ((isinstance(preconditioner, str) and preconditioner == "multilevel") or isinstance(preconditioner, MultilevelPreconditioner)):
+            raise ValueError("the multilevel preconditioner needs the matrix (its Galerkin values are formed from the values array): with a "
+                             f"TangentOperator the preconditioner must be one of {PRECONDITIONERS}")
         if isinstance(preconditioner, str) and preconditioner == "multilevel":
             pass  # built below, once everything else has been validated
         elif isinstance(preconditioner, MultilevelPreconditioner):
@@ -372,7 +459,12 @@ class ConjugateGradient:
                 raise TypeError(f"{name} must be an integer, got {type(v).__name__}")
             if v < least or v >= 2**31:
                 raise ValueError(f"{name} must lie in [{least}, 2^31), got {v}")
-        missing = np.flatnonzero(K.diag_block < 0)
+        if free:
+            missing = np.flatnonzero(K.valence == 0)
+            if missing.size:
+                raise ValueError(f"node {int(missing[0])} belongs to no cell: it has no diagonal block, its row is empty, the matrix singular")
+        else:
+            missing = np.flatnonzero(K.diag_block < 0)
         if missing.size:
             raise ValueError(f"node {int(missing[0])} has no diagonal block in the pattern: its row is empty, the matrix singular")
         if isinstance(preconditioner, str) and preconditioner == "multilevel":
@@ -386,6 +478,7 @@ class ConjugateGradient:
         self._code = self._ml._code if self._ml is not None else compile_kernels(K.gdim, preconditioner is not None)
         self.n = n
         self._work = {}  # device index -> (control, r, z, p, q, inv)
+        self._work_blocks = {}  # device index -> the block array of a TangentOperator's block-Jacobi
 
     # ---- what the compiler made ------------------------------------------------------------------------------------------------
     @property
@@ -419,12 +512,26 @@ class ConjugateGradient:
             w = self._work[dev] = (_Control(dev, self._op.nseg), *vectors, inv)
         return w
 
+    def _diagonal_blocks(self, dev: int):
+        """the block array of a ``TangentOperator``'s block-Jacobi, ``[n_nodes][D][D]``, one per device"""
+        blocks = self._work_blocks.get(dev)
+        if blocks is None:
+            import torch
+
+            blocks = self._work_blocks[dev] = torch.zeros(self.K.gdim**2 * self.K.n_nodes, dtype=torch.float64, device=torch.device("cuda", dev))
+        return blocks
+
     def __call__(self, values, b, x0=None, out=None) -> SolveResult:
-        """solve ``K x = b`` (synchronous at its end)"""
+        """solve ``K x = b`` (synchronous at its end); with a ``TangentOperator`` the first argument is the tangent of the quadrature
+        points: ``cg(tangent, b, x0=None, out=None)``"""
         import torch
 
         K, dev, n = self.K, self.device, self.n
-        K._check("values", values, K.nnz, dev)
+        free = isinstance(K, TangentOperator)  # (values is the tangent of the quadrature points then)
+        if free:
+            K._check("tangent", values, K.tangent_dim * K.n_points, dev)
+        else:
+            K._check("values", values, K.nnz, dev)
         K._check("b", b, n, dev)
         if x0 is not None:
             K._check("x0", x0, n, dev)
@@ -454,10 +561,14 @@ class ConjugateGradient:
             a.has_x0 = 0 if x0 is None else 1
             cap = BLOCKS_PER_CU * jit.num_cu(dev)
             ml = self._ml
+            if free and self.preconditioner:  # the nodes' own blocks without a matrix: a BSR values array over the diagonal pattern
+                a.values = K.diagonal_blocks(values, out=self._diagonal_blocks(dev)).data_ptr()
             if ml is not None:
                 ml._setup(dev, values, control)
             elif self.preconditioner:
                 jit.launch(self._code, dev, max(1, min(-(-K.n_nodes // 256), cap)), a, "ConjugateGradient inverse launch", kernel=INVERSE_KERNEL)
+            if free:
+                a.values = values.data_ptr()
             if x0 is not None:
                 op.apply(self._code, dev, a, x.data_ptr(), q.data_ptr(), _MODE_PLAIN)
             a.mode = _MODE_START

@@ -1,0 +1,358 @@
+"""The matrix-free tangent operator: ``y = K v`` and the nodes' own blocks of ``K`` from the tangent of the quadrature points.
+
+``TangentMatrix`` writes ``K = sum_p B_p^T C_p B_p w_p`` out as a sparse matrix -- 72 bytes per block next to a tangent array that
+sits in HBM anyway.  ``TangentOperator(force)`` applies the same matrix without forming it, constraints included, and is what
+``ConjugateGradient`` accepts in a ``TangentMatrix``'s place: the product with the ordered ``p . q`` behind it, and the diagonal
+blocks for block-Jacobi.  It covers ONE operator per mesh: the sums over the laws of several submeshes (``accumulate``,
+``pattern_dofmap``) are out of scope.
+
+Four run-time compiled kernels (``csrc/jit/tangent_operator.hip``, through ``jit.compile_program`` / ``jit.launch``), no
+floating-point atomics, ``-ffp-contract=off``.
+
+*The product.*  With ``M`` the 0/1 diagonal of the free dofs, ``y = M K M v + (I - M) v``: what the assembled matrix does with
+identity rows and columns at the constrained dofs.  The element kernel reads ``v`` through the dofmap (``+0.0`` at a constrained
+dof), forms the gradient of the point in registers by the producer's arithmetic (``gradient.py``: ``R`` over ``a`` ascending, then
+``G`` over ``k`` ascending) and goes on as the tangent form of ``internal_force.hip`` does (``force.py``: ``e``, ``s = C e``, ``T``,
+``fe``); no gradient array exists, and no gradient layout.  The node kernel adds every node's entries in ascending ``c*A + a``, gives
+a constrained dof ``v``'s own value, and forms the solver's ordered ``v . y`` as the rows complete.  The result is the bits of
+``force.tangent_action(tangent, op(where(mask, 0, v)))`` with ``v`` put back at the constrained dofs, for either layout of ``op``.
+
+*The diagonal blocks.*  For every cell and local node ``a`` the element kernel forms ``ke[c][a][.][a][.]`` by the arithmetic of
+``matrix.py``'s docstring (the zero entries of ``G`` and their products included), summed over ``q`` ascending, into a bounded
+scratch; the node kernel adds each node's entries in ascending ``c*A + a`` and writes the constrained rows and columns as the
+constants ``0.0`` and ``1.0``.  The cells go in ascending chunks of at most ``scratch_bytes``; the result is the bits of
+``K.diagonal_blocks(K(tangent))`` of a ``TangentMatrix`` of the same force and mask for every chunk size.  That equality needs the
+nodes of a cell to be distinct (a repeated node would add off-diagonal element entries to the block): a cell that names a node
+twice is refused.
+
+LDS of a block of either element kernel (``lds_bytes``): that of the force operator -- the reference table and four regions of
+``64 * D*D`` doubles; the same ``LDS_CAP``.  ``Q`` may be at most 64.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import jit
+from .force import MANDEL_DIM, MAX_POINTS_PER_CELL, VGPRS_PER_SIMD, InternalForce, cells_per_tile, kernel_resources
+from .gradient import BLOCKS_PER_CU, LDS_CAP, WAVES_LADDER, lds_bytes
+from .matrix import SCRATCH_BYTES
+
+ELEMENT_KERNEL = "fcamd_tangent_operator_element_kernel"
+NODE_KERNEL = "fcamd_tangent_operator_node_kernel"
+DIAGONAL_ELEMENT_KERNEL = "fcamd_tangent_operator_diagonal_element_kernel"
+DIAGONAL_NODE_KERNEL = "fcamd_tangent_operator_diagonal_node_kernel"
+KERNELS = (ELEMENT_KERNEL, NODE_KERNEL, DIAGONAL_ELEMENT_KERNEL, DIAGONAL_NODE_KERNEL)
+#: entries of a segment of the solver's ordered dot (solver.SEG)
+SEG = 3072
+#: the node kernel's modes: those of conjugate_gradient.hip
+MODE_ITERATE, MODE_PLAIN, MODE_QUIET = 1, 2, 3
+#: the most points of a slab of the diagonal-block kernel
+MAX_SLAB = 16
+
+__all__ = ["TangentOperator", "compile_kernels", "diagonal_cells_per_tile", "diagonal_slab", "lds_bytes", "program"]
+
+
+def diagonal_cells_per_tile(nodes_per_cell: int) -> int:
+    """the whole cells one wave of the diagonal-block kernel takes: ``64 // A`` (a lane per local node), at least one"""
+    return max(1, 64 // nodes_per_cell)
+
+
+def _even(n: int) -> int:
+    return (n + 1) // 2 * 2
+
+
+def diagonal_slab(gdim: int, nodes_per_cell: int, affine: bool) -> int:
+    """points of a slab of the diagonal-block kernel: the most (up to ``MAX_SLAB``) whose tangent rows, per-point inverse Jacobians,
+    basis gradients and weights fit a wave's region of ``64 * D*D`` doubles, every part padded to 16 bytes (``ValueError`` where not
+    even one point does)"""
+    s = MANDEL_DIM[gdim]
+    for slab in range(MAX_SLAB, 0, -1):
+        need = _even(slab * s * s) + (0 if affine else _even(slab * gdim * gdim)) + _even(slab * gdim * nodes_per_cell) + _even(slab)
+        if need <= 64 * gdim * gdim:
+            return slab
+    raise ValueError(f"the basis gradients of {nodes_per_cell} nodes x {gdim} at one point do not fit the wave's region of {64 * gdim * gdim} doubles "
+                     "of LDS")
+
+
+def program(gdim: int, nodes_per_cell: int, points_per_cell: int, affine: bool, slab: int, waves: int) -> str:
+    """the program text of one shape (the compile cache is keyed by it)"""
+    lines = [f"#define FCAMD_TO_D {int(gdim)}", f"#define FCAMD_TO_A {int(nodes_per_cell)}", f"#define FCAMD_TO_Q {int(points_per_cell)}",
+             f"#define FCAMD_TO_AFFINE {1 if affine else 0}", f"#define FCAMD_TO_SLAB {int(slab)}", f"#define FCAMD_TO_WAVES {int(waves)}",
+             '#include "tangent_operator.hip"']
+    return "\n".join(lines) + "\n"
+
+
+def compile_kernels(gdim: int, nodes_per_cell: int, points_per_cell: int, affine: bool, waves: int | None = None):
+    """The code object of one shape, all four kernels in it (no GPU needed).  ``waves``: that register budget of the element
+    kernels; ``None``: the first of ``WAVES_LADDER`` at which no kernel has scratch and the product's element kernel keeps to the
+    registers of that many waves.  A shape that spills at every budget, ``Q > 64`` or tables that do not fit the LDS: ``ValueError``.
+    ``code.waves`` is the budget kept, ``code.slab`` the slab of the diagonal blocks."""
+    if gdim not in (1, 2, 3):
+        raise ValueError(f"the geometric dimension must be 1, 2 or 3, got {gdim}")
+    if nodes_per_cell < 1 or points_per_cell < 1:
+        raise ValueError("a cell needs at least one node and one quadrature point")
+    if points_per_cell > MAX_POINTS_PER_CELL:
+        raise ValueError(f"a cell may have at most {MAX_POINTS_PER_CELL} quadrature points (a wave takes whole cells), got {points_per_cell}")
+    need = lds_bytes(gdim, nodes_per_cell, points_per_cell)
+    if need > LDS_CAP:
+        raise ValueError(f"the reference table of {points_per_cell} x {nodes_per_cell} x {gdim} doubles needs {need} bytes of LDS per block "
+                         f"with the wave regions; at most {LDS_CAP} fit")
+    slab = diagonal_slab(gdim, nodes_per_cell, affine)
+    name = f"tangent_operator_{gdim}d_{nodes_per_cell}n_{points_per_cell}q"
+    scratch = None
+    for w in WAVES_LADDER if waves is None else (waves,):
+        code = jit.compile_program(program(gdim, nodes_per_cell, points_per_cell, affine, slab, w), name, ELEMENT_KERNEL)
+        code.waves, code.slab = w, slab
+        if waves is not None:
+            return code
+        scratch = [kernel_resources(code.log, k)["scratch_bytes"] for k in KERNELS]
+        res = kernel_resources(code.log, ELEMENT_KERNEL)
+        # __launch_bounds__ is a hint: a budget the compiler overran is not the one the kernel runs at
+        if not any(scratch) and res["vgprs"] + (res["agprs"] or 0) <= VGPRS_PER_SIMD // w:
+            return code
+    raise ValueError(f"{name}: the kernels do not compile without scratch at any register budget (last: {scratch} bytes per lane)")
+
+
+class ElementArgs(C.Structure):
+    """ctypes mirror of ElementArgs (tangent_operator.hip)"""
+
+    _fields_ = [(name, C.c_void_p) for name in ("tangent", "v", "dofmap", "mask", "ref", "jinv", "weights", "fe", "sc")] + \
+               [("n_cells", C.c_int64), ("mode", C.c_int32), ("pad", C.c_int32)]
+
+
+class NodeArgs(C.Structure):
+    """ctypes mirror of NodeArgs (tangent_operator.hip)"""
+
+    _fields_ = [(name, C.c_void_p) for name in ("fe", "node_ptr", "adj", "v", "mask", "out", "partials", "sc")] + \
+               [("n_dofs", C.c_int64), ("nseg", C.c_int64), ("mode", C.c_int32), ("pad", C.c_int32)]
+
+
+class DiagElementArgs(C.Structure):
+    """ctypes mirror of DiagElementArgs (tangent_operator.hip)"""
+
+    _fields_ = [(name, C.c_void_p) for name in ("tangent", "ref", "jinv", "weights", "de")] + [("n_cells", C.c_int64)]
+
+
+class DiagNodeArgs(C.Structure):
+    """ctypes mirror of DiagNodeArgs (tangent_operator.hip)"""
+
+    _fields_ = [(name, C.c_void_p) for name in ("de", "node_ptr", "adj", "mask", "out")] + \
+               [("n_entries", C.c_int64), ("key_lo", C.c_int64), ("key_hi", C.c_int64), ("first", C.c_int32), ("pad", C.c_int32)]
+
+
+class TangentOperator:
+    """``A(tangent, v) -> y`` and ``A.diagonal_blocks(tangent)``: the tangent stiffness of the mesh of an ``InternalForce`` applied
+    without a matrix, on the GPU.
+
+    ``force``: the ``InternalForce`` whose operator (dofmap, reference gradients, inverse Jacobians, device), weights and node
+    adjacency are used; their device tables are shared, nothing they hold is uploaded again, and the element forces between the
+    product's two kernels live in ``force``'s own buffer.  One operator covers the whole mesh: sums over the laws of several
+    submeshes (``accumulate``, ``pattern_dofmap``) are out of scope.  ``scratch_bytes``: the most the cells' diagonal blocks may take
+    between the two kernels of ``diagonal_blocks`` (default ``matrix.SCRATCH_BYTES``; at least one tile of
+    ``diagonal_cells_per_tile`` cells); the result does not depend on it.
+
+    ``tangent`` is a float64 device tensor of ``S*S * n_points``, ``v`` one of ``D * n_nodes``; ``y`` is ``out`` or a new tensor
+    (``out`` must not alias ``v``).  ``set_constrained(mask)`` (bool ``[D n_nodes]``) makes the rows and columns of the constrained
+    dofs the identity's: ``y = v`` there, ``v`` counts as ``+0.0`` there elsewhere; the diagonal blocks get the constants ``1.0`` and
+    ``0.0``.
+
+    Everything is validated on the host before anything is uploaded or launched (``TypeError`` / ``ValueError`` as for
+    ``InternalForce`` and ``TangentMatrix``); a cell that names a node twice, ``Q > 64`` and the LDS cap are refused at construction.
+    The kernels are compiled at construction (no GPU needed).  All launches go to torch's current stream and are asynchronous; the
+    buffers between the kernels belong to the objects: use one from one stream at a time."""
+
+    def __init__(self, force: InternalForce, scratch_bytes: int | None = None):
+        if not isinstance(force, InternalForce):
+            raise TypeError(f"force must be an InternalForce, got {type(force).__name__}")
+        if scratch_bytes is None:
+            scratch_bytes = SCRATCH_BYTES
+        if isinstance(scratch_bytes, bool) or not isinstance(scratch_bytes, (int, np.integer)):
+            raise TypeError(f"scratch_bytes must be an integer, got {type(scratch_bytes).__name__}")
+        op = force.op
+        d_, a_, q_ = op.gdim, op.nodes_per_cell, op.points_per_cell
+        cw = diagonal_cells_per_tile(a_)
+        if scratch_bytes < cw * a_ * d_ * d_ * 8:
+            raise ValueError(f"scratch_bytes = {scratch_bytes} does not hold one tile of {cw} cells' diagonal blocks of {a_} x {d_} x {d_} doubles "
+                             f"({cw * a_ * d_ * d_ * 8} bytes)")
+        rows = np.sort(op._dofmap, axis=1)
+        twice = np.flatnonzero((rows[:, 1:] == rows[:, :-1]).any(axis=1))
+        if twice.size:
+            raise ValueError(f"cell {int(twice[0])} names a node twice: its off-diagonal element entries would belong to the node's own block")
+        self._code = compile_kernels(d_, a_, q_, op.affine)  # (raises the ValueError of Q > 64, of the LDS cap and of the registers)
+        self.force, self.op = force, op
+        self.gdim, self.nodes_per_cell, self.points_per_cell = d_, a_, q_
+        self.n_cells, self.n_points, self.n_nodes = op.n_cells, op.n_points, op.n_nodes
+        self.tangent_dim = MANDEL_DIM[d_] ** 2
+        self.shape = (d_ * op.n_nodes, d_ * op.n_nodes)
+        self.scratch_bytes = int(scratch_bytes)
+        self.diagonal_cells_per_tile = cw
+        self.chunk_cells = int(scratch_bytes) // (a_ * d_ * d_ * 8) // cw * cw  # whole tiles
+        #: cells of every node: a node of none has an empty row
+        self.valence = np.diff(force.node_ptr.astype(np.int64))
+        self._mask = None
+        self._mask_version = 0
+        self._mask_on = {}  # device index -> (version, mask tensor)
+        self._scratch = {}  # device index -> the diagonal blocks of a chunk's cells
+
+    # ---- what the compiler made ------------------------------------------------------------------------------------------------
+    @property
+    def resources(self) -> dict:
+        """``{"vgprs", "sgprs", "scratch_bytes", "lds_bytes", "waves_per_simd", ...}`` of the product's element kernel, under "node",
+        "diagonal_element" and "diagonal_node" those of the other kernels (compiler remarks), under "waves" the register budget
+        kept and under "slab" the points per slab of the diagonal blocks"""
+        r = kernel_resources(self._code.log, ELEMENT_KERNEL)
+        for name, kernel in (("node", NODE_KERNEL), ("diagonal_element", DIAGONAL_ELEMENT_KERNEL), ("diagonal_node", DIAGONAL_NODE_KERNEL)):
+            r[name] = kernel_resources(self._code.log, kernel)
+        r["waves"], r["slab"] = self._code.waves, self._code.slab
+        return r
+
+    @property
+    def compile_log(self) -> str:
+        return self._code.log
+
+    def lds_bytes(self) -> int:
+        """LDS of one block of either element kernel"""
+        return lds_bytes(self.gdim, self.nodes_per_cell, self.points_per_cell)
+
+    @property
+    def device(self) -> int:
+        return self.op.device
+
+    # ---- constraints -----------------------------------------------------------------------------------------------------------
+    def set_constrained(self, mask) -> None:
+        """``mask``: bool ``[D n_nodes]``, true at the Dirichlet dofs, or ``None``.  Uploaded at the next call, and again only when
+        it changes.  A constrained dof whose node belongs to no cell is a ``ValueError``, as it is for ``TangentMatrix``"""
+        if mask is None:
+            if self._mask is not None:
+                self._mask, self._mask_version = None, self._mask_version + 1
+            return
+        if not isinstance(mask, np.ndarray):
+            raise TypeError(f"mask must be a numpy.ndarray or None, got {type(mask).__name__}")
+        if mask.dtype != np.bool_:
+            raise TypeError(f"mask must be bool, got {mask.dtype}")
+        if mask.shape != (self.shape[0],):
+            raise ValueError(f"mask must have shape {(self.shape[0],)} (one entry per dof), got {mask.shape}")
+        nodes = np.flatnonzero(mask) // self.gdim
+        missing = nodes[self.valence[nodes] == 0]
+        if missing.size:
+            raise ValueError(f"node {int(missing[0])} has a constrained dof and belongs to no cell: it has no diagonal block to make the identity's")
+        if self._mask is None or not np.array_equal(self._mask, mask):
+            self._mask, self._mask_version = np.ascontiguousarray(mask).copy(), self._mask_version + 1
+
+    def _mask_table(self, dev: int):
+        if self._mask is None:
+            return None
+        have = self._mask_on.get(dev)
+        if have is None or have[0] != self._mask_version:
+            import torch
+
+            from .hostio import to_device
+
+            d = torch.device("cuda", dev)
+            with torch.cuda.device(d):
+                have = self._mask_on[dev] = (self._mask_version, to_device(self._mask.view(np.uint8), d))
+        return have[1]
+
+    def _check(self, name: str, a, numel: int, dev: int):
+        self.force._check(name, a, numel, dev)
+
+    # ---- the product -----------------------------------------------------------------------------------------------------------
+    def _apply(self, dev: int, tangent_ptr: int, v_ptr: int, out_ptr: int, mode: int, partials_ptr: int = 0, control_ptr: int = 0) -> None:
+        """both launches of ``out = A v`` on pointers that have been validated (the solver's seam); ``mode``: ``MODE_QUIET`` -- the
+        product alone --, ``MODE_PLAIN`` -- the ordered ``v . out`` into the control block's ``dot`` --, ``MODE_ITERATE`` -- into ``pq``, under
+        the status"""
+        import torch
+
+        force, op = self.force, self.op
+        nd = self.shape[0]
+        _, node_ptr, adj = force._tables(dev)
+        mask = self._mask_table(dev)
+        mask_ptr = 0 if mask is None else mask.data_ptr()
+        cap = BLOCKS_PER_CU * jit.num_cu(dev)
+        fe_ptr = 0
+        if self.n_cells:
+            dofmap, ref, jinv, _ = op._tables(dev)
+            weights = force._tables(dev)[0]
+            fe = force._fe.get(dev)
+            if fe is None:
+                fe = force._fe[dev] = torch.empty(self.n_cells * self.nodes_per_cell * self.gdim, dtype=torch.float64, device=torch.device("cuda", dev))
+            fe_ptr = fe.data_ptr()
+            tiles = -(-self.n_cells // cells_per_tile(self.gdim, self.points_per_cell))
+            ea = ElementArgs(tangent_ptr, v_ptr, dofmap.data_ptr(), mask_ptr, ref.data_ptr(), jinv.data_ptr(), weights.data_ptr(), fe_ptr,
+                             control_ptr, self.n_cells, mode, 0)
+            jit.launch(self._code, dev, min((tiles + 3) // 4, cap), ea, "TangentOperator element launch")  # a wave per tile, 4 waves per block
+        nseg = -(-nd // SEG)
+        na = NodeArgs(fe_ptr, node_ptr.data_ptr(), adj.data_ptr(), v_ptr, mask_ptr, out_ptr, partials_ptr, control_ptr, nd, nseg, mode, 0)
+        jit.launch(self._code, dev, max(1, min(nseg, cap)), na, "TangentOperator node launch", kernel=NODE_KERNEL)  # a block per segment
+
+    def __call__(self, tangent, v, out=None):
+        """``y = M K M v + (I - M) v`` for this tangent (asynchronous, on torch's current stream)"""
+        import torch
+
+        dev = self.device
+        nd = self.shape[0]
+        self._check("tangent", tangent, self.tangent_dim * self.n_points, dev)
+        self._check("v", v, nd, dev)
+        if out is not None:
+            self._check("out", out, nd, dev)
+            if _overlap(out, v):
+                raise ValueError("out must not alias v")
+        with torch.cuda.device(dev):
+            if out is None:
+                out = torch.empty(nd, dtype=torch.float64, device=torch.device("cuda", dev))
+            self._apply(dev, tangent.data_ptr(), v.data_ptr(), out.data_ptr(), MODE_QUIET)
+        return out
+
+    # ---- the diagonal blocks ---------------------------------------------------------------------------------------------------
+    def chunks(self):
+        """the ascending cell ranges ``(first, end)`` ``diagonal_blocks`` runs one after the other"""
+        return [(c, min(c + self.chunk_cells, self.n_cells)) for c in range(0, self.n_cells, self.chunk_cells)]
+
+    def diagonal_blocks(self, tangent, out=None):
+        """device tensor ``[n_nodes][D][D]``: every node's own block of the constrained ``K`` (zeros at a node of no cell) --
+        ``out`` or a new one (asynchronous, on torch's current stream)"""
+        import torch
+
+        dev = self.device
+        d_, a_, q_ = self.gdim, self.nodes_per_cell, self.points_per_cell
+        dd = d_ * d_
+        self._check("tangent", tangent, self.tangent_dim * self.n_points, dev)
+        if out is not None:
+            self._check("out", out, dd * self.n_nodes, dev)
+        with torch.cuda.device(dev):
+            d = torch.device("cuda", dev)
+            if out is None:
+                out = torch.empty((self.n_nodes, d_, d_), dtype=torch.float64, device=d)
+            _, node_ptr, adj = self.force._tables(dev)
+            mask = self._mask_table(dev)
+            cap = BLOCKS_PER_CU * jit.num_cu(dev)
+            na = DiagNodeArgs(0, node_ptr.data_ptr(), adj.data_ptr(), 0 if mask is None else mask.data_ptr(), out.data_ptr(), dd * self.n_nodes,
+                              0, 0, 1, 0)
+            node_blocks = max(1, min((dd * self.n_nodes + 255) // 256, cap))  # a lane per entry
+            if self.n_cells == 0:  # no contributions: the entries are started and left
+                jit.launch(self._code, dev, node_blocks, na, "TangentOperator diagonal node launch", kernel=DIAGONAL_NODE_KERNEL)
+                return out
+            _, ref, jinv, _ = self.op._tables(dev)
+            weights = self.force._tables(dev)[0]
+            de = self._scratch.get(dev)
+            if de is None:
+                de = self._scratch[dev] = torch.empty(min(self.chunk_cells, self.n_cells) * a_ * dd, dtype=torch.float64, device=d)
+            na.de = de.data_ptr()
+            jstride = 8 * dd * (1 if self.op.affine else q_)
+            for k, (c0, c1) in enumerate(self.chunks()):
+                ea = DiagElementArgs(tangent.data_ptr() + 8 * self.tangent_dim * q_ * c0, ref.data_ptr(), jinv.data_ptr() + jstride * c0,
+                                     weights.data_ptr() + 8 * q_ * c0, de.data_ptr(), c1 - c0)
+                tiles = -(-(c1 - c0) // self.diagonal_cells_per_tile)
+                jit.launch(self._code, dev, min((tiles + 3) // 4, cap), ea, "TangentOperator diagonal element launch",
+                           kernel=DIAGONAL_ELEMENT_KERNEL)  # a wave per tile, 4 waves per block
+                na.key_lo, na.key_hi, na.first = c0 * a_, c1 * a_, 1 if k == 0 else 0
+                jit.launch(self._code, dev, node_blocks, na, "TangentOperator diagonal node launch", kernel=DIAGONAL_NODE_KERNEL)
+        return out
+
+
+def _overlap(a, b) -> bool:
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + 8 * b.numel() and b0 < a0 + 8 * a.numel()

@@ -16,5 +16,6 @@ from ._api import __version__  # noqa: E402,F401
 from .bicgstab import BiCGStab  # noqa: E402,F401
 from .multilevel import MultilevelPreconditioner  # noqa: E402,F401
 from .solver import ConjugateGradient  # noqa: E402,F401
+from .tangent_operator import TangentOperator  # noqa: E402,F401
 
-__all__ = [*_api_all, "BiCGStab", "ConjugateGradient", "MultilevelPreconditioner"]
+__all__ = [*_api_all, "BiCGStab", "ConjugateGradient", "MultilevelPreconditioner", "TangentOperator"]
