@@ -59,6 +59,24 @@ sizes.  Two programs per object: the fine one (``FCAMD_CG_D = D``, the object's 
 coarse one (``FCAMD_CG_D = Dc``: every level ``l >= 1`` and the ``(Dc, Dc)`` transfer kernels).  A level-0 aggregate whose columns of ``P``
 are linearly dependent -- a lone node, all members at one point, in 3-D all members on one line -- is refused at construction.
 
+*On a matrix-free operator* (``MultilevelPreconditioner(A)`` with a ``TangentOperator``; csrc/jit/multilevel_free.hip; translations
+only).  The hierarchy is that of ``matrix.block_pattern(dofmap, n_nodes)``: every table is the one of a ``TangentMatrix`` of the same
+force (a node of no cell, which that matrix would refuse, has a row of its own block).  Nothing reads fine values: the first argument of ``setup``, ``apply`` and the solve is the tangent of the quadrature points.
+*Level-1 values*, coarse block ``(I, J)``, entry ``(r, s)``: ``f`` = the number of constrained dofs ``D i + r`` among the members ``i`` of
+``I``, as a double, if ``I == J`` and ``r == s``, else ``0.0``; over the contributions ``(c, a, b)`` with ``agg[dofmap[c][a]] == I`` and
+``agg[dofmap[c][b]] == J``, ascending in ``c A A + a A + b``: nothing where dof ``D dofmap[c][a] + r`` or dof ``D dofmap[c][b] + s`` is
+constrained, else ``f = f + ke[c][a][r][b][s]`` (``ke``: the element matrix of ``matrix.py``'s docstring, on the bits, from its element
+kernel).  This is ``P^T (M K M + I - M) P``, the Galerkin step of the assembled route in another order of summation: equal to it
+within rounding, not on the bits.  The remark on the constrained dofs carries over: each adds ``1.0`` to its aggregate's coarse
+diagonal, a fully constrained aggregate stays non-singular and ``M`` symmetric positive definite.  The element matrices pass through
+a scratch of at most ``A.scratch_bytes`` in ascending whole-tile chunks of cells, ``(A D)^2 * 8`` bytes per cell; a later chunk goes
+on from the value that is there, so the bits do not depend on the chunk size.  *Level 0 of the cycle*: the block array is
+``A.diagonal_blocks(tangent)``, inverted by the solver's inverse kernel through the diagonal table ``0 .. n`` (what block-Jacobi on
+an operator does); a product of the multiplicative cycle is the operator's two launches in quiet mode, which does not look at
+the status: behind the end of a solve such a product still writes the preconditioner's own ``q``, which no kernel reads then.
+Restriction, prolongation (skipped at the operator's constrained dofs), smoothing, the closing kernel and the levels ``l >= 2`` are
+the kernels above, unchanged.
+
 LDS of a block: ``lds_bytes(kernel)``.
 """
 
@@ -69,9 +87,11 @@ import ctypes as C
 import numpy as np
 
 from . import jit, solver
+from . import matrix as _matrix
 from .force import kernel_resources
 from .gradient import BLOCKS_PER_CU
 from .matrix import TangentMatrix
+from .tangent_operator import TangentOperator
 
 GALERKIN_KERNEL = "fcamd_ml_galerkin_kernel"
 RESTRICT_KERNEL = "fcamd_ml_restrict_kernel"
@@ -83,6 +103,7 @@ RIGID_GALERKIN_KERNEL = "fcamd_mr_galerkin_kernel"
 RIGID_RESTRICT_KERNEL = "fcamd_mr_restrict_kernel"
 RIGID_PROLONG_KERNEL = "fcamd_mr_prolong_kernel"
 RIGID_KERNELS = (RIGID_GALERKIN_KERNEL, RIGID_RESTRICT_KERNEL, RIGID_PROLONG_KERNEL)
+FREE_GALERKIN_KERNEL = "fcamd_mf_galerkin_kernel"
 CYCLES = ("multiplicative", "additive")
 COARSE_SPACES = ("translations", "rigid_body")
 _MODE_QUIET = 3
@@ -90,8 +111,8 @@ _MODE_QUIET = 3
 #: gradients, two in BiCGStab (p -> y, s -> z), and the standalone ``apply`` beside them
 PLANS = 4
 
-__all__ = ["MultilevelPreconditioner", "aggregate", "coarse_dofs", "coarsen", "compile_kernels", "compile_rigid_kernels", "hierarchy", "lds_bytes",
-           "place", "program", "rigid_program"]
+__all__ = ["MultilevelPreconditioner", "aggregate", "coarse_dofs", "coarsen", "compile_free_kernels", "compile_kernels", "compile_rigid_kernels",
+           "free_program", "hierarchy", "lds_bytes", "place", "program", "rigid_program"]
 
 
 def lds_bytes(kernel: str = CLOSE_KERNEL) -> int:
@@ -99,7 +120,7 @@ def lds_bytes(kernel: str = CLOSE_KERNEL) -> int:
     nor in the three of the rigid-body coarse space; the solver's kernels of the same program: ``solver.lds_bytes(kernel, False)``"""
     if kernel in solver.KERNELS:
         return solver.lds_bytes(kernel, False)
-    if kernel in RIGID_KERNELS:
+    if kernel in RIGID_KERNELS or kernel == FREE_GALERKIN_KERNEL:
         return 0
     return {CLOSE_KERNEL: 8 * (256 + 2), GALERKIN_KERNEL: 0, RESTRICT_KERNEL: 0, PROLONG_KERNEL: 0, SMOOTH_KERNEL: 0}[kernel]
 
@@ -148,6 +169,26 @@ def compile_rigid_kernels(gdim: int):
                 raise ValueError(f"{name}: {kernel} compiles with {scratch} bytes of scratch per lane")
         codes.append(code)
     return tuple(codes)
+
+
+def free_program(gdim: int, nodes_per_cell: int) -> str:
+    """the program text of the first Galerkin step of a ``TangentOperator``: level 1 from the element matrices"""
+    return "\n".join([f"#define FCAMD_MF_D {int(gdim)}", f"#define FCAMD_MF_A {int(nodes_per_cell)}", '#include "multilevel_free.hip"']) + "\n"
+
+
+def compile_free_kernels(gdim: int, nodes_per_cell: int):
+    """The code object of the first Galerkin step of a ``TangentOperator`` of one cell shape (no GPU needed).  Scratch is a
+    ``ValueError``."""
+    if gdim not in (1, 2, 3):
+        raise ValueError(f"the dofs per node must be 1, 2 or 3, got {gdim}")
+    if nodes_per_cell < 1:
+        raise ValueError("a cell needs at least one node")
+    name = f"multilevel_free_{gdim}d_{nodes_per_cell}n"
+    code = jit.compile_program(free_program(gdim, nodes_per_cell), name, FREE_GALERKIN_KERNEL)
+    scratch = kernel_resources(code.log, FREE_GALERKIN_KERNEL)["scratch_bytes"]
+    if scratch:
+        raise ValueError(f"{name}: {FREE_GALERKIN_KERNEL} compiles with {scratch} bytes of scratch per lane")
+    return code
 
 
 # ---- the hierarchy (host) --------------------------------------------------------------------------------------------------------
@@ -266,6 +307,143 @@ class Args(C.Structure):
                 ("first", C.c_int32), ("plain", C.c_int32), ("use_q", C.c_int32), ("start", C.c_int32)]
 
 
+class FreeArgs(C.Structure):
+    """ctypes mirror of fcamd_mf::Args (multilevel_free.hip)"""
+
+    _fields_ = [(name, C.c_void_p) for name in ("ke", "blk_ptr", "contrib", "dofmap", "mask", "block_row", "block_col", "mem_ptr", "members", "values")] + \
+               [("entry0", C.c_int64), ("n_entries", C.c_int64), ("key_lo", C.c_int64), ("key_hi", C.c_int64), ("cell0", C.c_int64),
+                ("first", C.c_int32), ("pad", C.c_int32)]
+
+
+# ---- the seam of level 0 -----------------------------------------------------------------------------------------------------------
+# What the preconditioner asks of its fine level, and nothing else reads ``K``: the pattern the hierarchy is built from, the check of
+# the first argument of a call, the array the inverse kernel reads the nodes' own blocks from, the launches of a product, the first
+# Galerkin step, and the device pointers of all that a cached launch plan holds.
+class _AssembledFine:
+    """level 0 is a ``TangentMatrix``: its values array is read where ``dest_base`` / ``dest_stride`` say"""
+
+    free = False
+
+    def __init__(self, K: TangentMatrix):
+        self.K = K
+        self.indptr, self.indices = K.indptr, K.indices
+        self.missing = np.flatnonzero(K.diag_block < 0)
+
+    def check(self, values, dev: int) -> None:
+        self.K._check("values", values, self.K.nnz, dev)
+
+    def blocks(self, pc, dev: int, values) -> int:
+        """the pointer the inverse kernel of level 0 reads through the operator's diagonal table: the values themselves"""
+        return values.data_ptr()
+
+    def product(self, pc, dev: int, values, control, x_ptr: int, q_ptr: int, cap: int) -> list:
+        a = pc._level_args(dev, 0, values, control)
+        a.va, a.q, a.mode = x_ptr, q_ptr, _MODE_QUIET
+        return [(pc._code, solver.MATVEC_KERNEL, max(1, min(int(a.nseg), cap)), a, "MultilevelPreconditioner matrix-vector launch")]
+
+    def key(self, pc, dev: int) -> tuple:
+        return tuple(t.data_ptr() for t in pc._op.tables(dev))
+
+
+class _FreeFine:
+    """Level 0 is a ``TangentOperator``: there is no values array.  The nodes' own blocks are ``A.diagonal_blocks(tangent)`` in a block
+    array of the preconditioner's, a product is the operator's two launches in quiet mode, and the values of level 1 are gathered
+    from the element matrices of ``fcamd_tangent_matrix_element_kernel`` -- compiled here through ``matrix.compile_kernels``, no
+    ``TangentMatrix`` is constructed -- which pass in ascending whole-tile chunks through a scratch of at most ``A.scratch_bytes``."""
+
+    free = True
+
+    def __init__(self, A: TangentOperator):
+        self.K = A
+        d_, a_ = A.gdim, A.nodes_per_cell
+        m = a_ * d_
+        self.cells_per_tile = cw = _matrix.cells_per_tile(d_, a_)
+        if A.scratch_bytes < cw * m * m * 8:
+            raise ValueError(f"the operator's scratch_bytes = {A.scratch_bytes} does not hold one tile of {cw} element matrices of {m} x {m} doubles "
+                             f"({cw * m * m * 8} bytes): the multilevel preconditioner forms its first coarse level from them")
+        self.chunk_cells = A.scratch_bytes // (m * m * 8) // cw * cw  # whole tiles
+        # the pattern of the TangentMatrix of the same force; a node of no cell (that matrix would lack its diagonal block) gets a row of
+        # its own block, as a pattern_dofmap with a cell of its own would give it: the block is zero, the status of a setup singular_block
+        unused = np.flatnonzero(A.valence == 0).astype(np.int32)
+        cells = A.op._dofmap if not unused.size else np.concatenate([A.op._dofmap, np.repeat(unused[:, None], a_, axis=1)])
+        self.indptr, self.indices = _matrix.block_pattern(cells, A.n_nodes)
+        self.missing = np.zeros(0, dtype=np.int64)
+        self.element_code = self.gather_code = None
+        self.blk_ptr = self.contributions = self.block_row = None
+        self.chunk_blocks = []
+
+    def chunks(self):
+        """the ascending cell ranges ``(first, end)`` whose element matrices pass through the scratch one after the other"""
+        n = self.K.n_cells
+        return [(c, min(c + self.chunk_cells, n)) for c in range(0, n, self.chunk_cells)]
+
+    def build(self, levels: list) -> None:
+        """the programs and, with a coarse level, its contribution lists (host)"""
+        A = self.K
+        d_, a_ = A.gdim, A.nodes_per_cell
+        self.element_code = _matrix.compile_kernels(d_, a_, A.points_per_cell, A.op.affine)  # (no kernel of it has scratch, or this raises)
+        self.gather_code = compile_free_kernels(d_, a_)
+        if len(levels) < 2:
+            return
+        fine, coarse = levels[0], levels[1]
+        self.blk_ptr, self.contributions = _matrix.contribution_lists(fine.agg[A.op._dofmap], coarse.n_nodes, coarse.indptr, coarse.indices)
+        self.block_row = coarse.block_row
+        if A.n_cells and coarse.nnzb:  # the range of coarse blocks every chunk's cells touch: a later chunk's gather runs over it alone
+            block_of = np.empty(self.contributions.size, dtype=np.int32)  # by c*A*A + a*A + b
+            block_of[self.contributions] = np.repeat(np.arange(coarse.nnzb, dtype=np.int32), np.diff(self.blk_ptr))
+            starts = np.arange(0, A.n_cells, self.chunk_cells, dtype=np.int64) * (a_ * a_)
+            self.chunk_blocks = list(zip(np.minimum.reduceat(block_of, starts).tolist(), (np.maximum.reduceat(block_of, starts) + 1).tolist()))
+
+    def check(self, tangent, dev: int) -> None:
+        self.K._check("tangent", tangent, self.K.tangent_dim * self.K.n_points, dev)
+
+    def blocks(self, pc, dev: int, tangent) -> int:
+        """the nodes' own blocks, formed now by the operator's two diagonal kernels (asynchronous): a BSR values array over the
+        diagonal pattern, which is what the operator's diagonal table ``0 .. n`` makes of it"""
+        return self.K.diagonal_blocks(tangent, out=pc._device(dev).blocks).data_ptr()
+
+    def product(self, pc, dev: int, tangent, control, x_ptr: int, q_ptr: int, cap: int) -> list:
+        # (quiet mode neither reads nor writes the control block: a product enqueued behind the end of a solve writes the
+        # preconditioner's own q and nothing else, and every kernel that would read q returns at once)
+        return self.K._launches(dev, tangent.data_ptr(), x_ptr, q_ptr, _MODE_QUIET)
+
+    def key(self, pc, dev: int) -> tuple:
+        # (the element forces between the product's two kernels are ``force``'s own buffer: made once, kept as long as the operator)
+        A = self.K
+        held = [*pc._op.tables(dev), *A.force._tables(dev)] + ([*A.op._tables(dev)[:3]] if A.n_cells else [])
+        return tuple(t.data_ptr() for t in held)
+
+    def galerkin(self, pc, dev: int, tangent, cap: int) -> None:
+        """the values of level 1 from the tangent: per chunk the element kernel, then the gather of multilevel_free.hip"""
+        import torch
+
+        A, on = self.K, pc._device(dev)
+        d_, a_, q_ = A.gdim, A.nodes_per_cell, A.points_per_cell
+        m = a_ * d_
+        dd = d_ * d_
+        dofmap, ref, jinv, _ = A.op._tables(dev)
+        weights = A.force._tables(dev)[0]
+        mask = A._mask_table(dev)
+        t0, t1 = on.tables[0], on.tables[1]
+        n_entries = dd * pc._levels[1].nnzb
+        ga = FreeArgs(on.ke.data_ptr(), t1["blk_ptr"].data_ptr(), t1["contrib"].data_ptr(), dofmap.data_ptr(), 0 if mask is None else mask.data_ptr(),
+                      t1["block_row"].data_ptr(), t1["indices"].data_ptr(), t0["mem_ptr"].data_ptr(), t0["members"].data_ptr(), on.values[1].data_ptr(),
+                      0, n_entries, 0, 0, 0, 1, 0)
+        gather_blocks = pc._blocks(n_entries, cap)  # a lane per entry
+        jstride = 8 * dd * (1 if A.op.affine else q_)
+        with torch.cuda.device(dev):
+            for k, (c0, c1) in enumerate(self.chunks()):
+                ea = _matrix.ElementArgs(tangent.data_ptr() + 8 * A.tangent_dim * q_ * c0, ref.data_ptr(), jinv.data_ptr() + jstride * c0,
+                                         weights.data_ptr() + 8 * q_ * c0, on.ke.data_ptr(), c1 - c0)
+                tiles = -(-(c1 - c0) // self.cells_per_tile)
+                jit.launch(self.element_code, dev, min((tiles + 3) // 4, cap), ea, "MultilevelPreconditioner element launch")  # a wave per tile, 4 waves per block
+                ga.key_lo, ga.key_hi, ga.cell0, ga.first = c0 * a_ * a_, c1 * a_ * a_, c0, 1 if k == 0 else 0
+                if k:  # the first chunk starts every entry; a later one visits the coarse blocks its cells touch
+                    ga.entry0, ga.n_entries = dd * self.chunk_blocks[k][0], dd * self.chunk_blocks[k][1]
+                    gather_blocks = pc._blocks(ga.n_entries - ga.entry0, cap)
+                jit.launch(self.gather_code, dev, gather_blocks, ga, "MultilevelPreconditioner first Galerkin launch")
+
+
 class _OnDevice:
     """the hierarchy's tables, values and vectors on one device"""
 
@@ -291,12 +469,21 @@ class _OnDevice:
                 self.b.append(zeros(dofs[l] * lv.n_nodes))
                 self.x.append(zeros(dofs[l] * lv.n_nodes))
             if lv.agg is not None:
-                for name in ("agg", "mem_ptr", "members", "fold_ptr", "fold") + (("block_row", "indices", "offset") if pc._rigid else ()):
+                # (an operator's level 0 has no blocks to fold: its fold lists, as long as the fine pattern, stay on the host)
+                folds = () if l == 0 and pc._seam.free else ("fold_ptr", "fold")
+                for name in ("agg", "mem_ptr", "members") + folds + (("block_row", "indices", "offset") if pc._rigid else ()):
                     if name not in t:  # (a coarse level's column nodes are there already)
                         t[name] = to_device(getattr(lv, name), d)
+            if l == 1 and pc._seam.free:  # the lists of the first Galerkin step
+                t["blk_ptr"], t["contrib"], t["block_row"] = (to_device(x, d) for x in (pc._seam.blk_ptr, pc._seam.contributions, pc._seam.block_row))
             self.tables.append(t)
             self.inv.append(zeros(dofs[l]**2 * lv.n_nodes))
             self.q.append(zeros(dofs[l] * lv.n_nodes))
+        if pc._seam.free:  # the nodes' own blocks of level 0 and, with a coarse level, the element matrices of a chunk of cells
+            A, seam = pc.K, pc._seam
+            self.blocks = zeros(A.gdim**2 * A.n_nodes)[: A.gdim**2 * A.n_nodes]
+            if len(pc._levels) > 1:
+                self.ke = zeros(min(seam.chunk_cells, A.n_cells) * (A.nodes_per_cell * A.gdim)**2)
         self.control = None  # of setup() and apply()
         self.plans = {}  # key -> (launch plan, what it keeps alive), the last PLANS used
 
@@ -320,16 +507,27 @@ class MultilevelPreconditioner:
     nodes of the levels ``l >= 1`` carry ``coarse_dofs`` = 6 (3-D) or 3 (2-D) dofs (module docstring; 1-D: the translation
     hierarchy).  A level-0 aggregate whose rigid-body modes are linearly dependent -- a lone node, all members at one point, in 3-D
     all on one line -- is a ``ValueError`` that names it, raised before anything is compiled.  ``positions(l)`` and ``offsets(l)``
-    show where the nodes were placed."""
+    show where the nodes were placed.
+
+    ``K`` may be a ``TangentOperator`` instead (module docstring, "On a matrix-free operator"): the hierarchy is that of the
+    ``TangentMatrix`` of the same force, ``setup(tangent)``, ``apply(tangent, r, out=None)`` and ``ConjugateGradient(A, preconditioner=pc)(tangent,
+    b)`` take the ``S*S n_points`` tangent where the values stood, and no matrix is formed: level 1 is gathered from the element matrices,
+    which pass through a scratch of ``A.scratch_bytes`` (less than one tile of ``matrix.cells_per_tile`` element matrices: a
+    ``ValueError``).  Translations only: ``coarse_space="rigid_body"`` on an operator is a ``ValueError``.  A node in no cell has a zero
+    block of its own on every level it reaches: ``setup`` and ``apply`` end with the status ``singular_block`` (nothing is applied), and
+    ``ConjugateGradient`` refuses such an operator at construction."""
 
     def __init__(self, K: TangentMatrix, cycle: str = "multiplicative", smoothing: int = 1, omega: float = 0.5, coarsest_nodes: int = 64,
                  coarsest_sweeps: int = 8, max_levels: int = 10, coarse_space: str = "translations", coordinates=None):
-        if not isinstance(K, TangentMatrix):
-            raise TypeError(f"K must be a TangentMatrix, got {type(K).__name__}")
+        if not isinstance(K, (TangentMatrix, TangentOperator)):
+            raise TypeError(f"K must be a TangentMatrix or a TangentOperator, got {type(K).__name__}")
         if cycle not in CYCLES:
             raise ValueError(f"cycle must be one of {CYCLES}, got {cycle!r}")
         if not (isinstance(coarse_space, str) and coarse_space in COARSE_SPACES):
             raise ValueError(f"coarse_space must be one of {COARSE_SPACES}, got {coarse_space!r}")
+        if isinstance(K, TangentOperator) and coarse_space != "translations":
+            raise ValueError(f"coarse_space={coarse_space!r} needs the matrix: on a TangentOperator the first Galerkin step is the sum of the element matrices, "
+                             'which is P^T K P for the translations only (with rotations it is P_i^T ke P_j with the offsets); use coarse_space="translations"')
         if coarse_space == "translations":
             if coordinates is not None:
                 raise ValueError('coordinates belong to coarse_space="rigid_body"; the translations need none')
@@ -353,14 +551,15 @@ class MultilevelPreconditioner:
                 raise TypeError(f"{name} must be an integer, got {type(v).__name__}")
             if v < 1 or v >= 2**31:
                 raise ValueError(f"{name} must lie in [1, 2^31), got {v}")
-        missing = np.flatnonzero(K.diag_block < 0)
-        if missing.size:
-            raise ValueError(f"node {int(missing[0])} has no diagonal block in the pattern: its row is empty, the matrix singular")
+        seam = _FreeFine(K) if isinstance(K, TangentOperator) else _AssembledFine(K)  # (an operator: raises the ValueError of its scratch)
+        if seam.missing.size:
+            raise ValueError(f"node {int(seam.missing[0])} has no diagonal block in the pattern: its row is empty, the matrix singular")
         self.K = K
+        self._seam = seam
         # fixed for the life of the object (read-only properties below): the launch plan of a cycle is built from them
         self._cycle_name, self._smoothing, self._omega = cycle, int(smoothing), float(omega)
         self._coarsest_nodes, self._coarsest_sweeps, self._max_levels = int(coarsest_nodes), int(coarsest_sweeps), int(max_levels)
-        self._levels = hierarchy(K.indptr, K.indices, self.coarsest_nodes, self.max_levels)
+        self._levels = hierarchy(seam.indptr, seam.indices, self.coarsest_nodes, self.max_levels)
         for l, lv in enumerate(self._levels):
             missing = np.flatnonzero(lv.diag_block < 0)
             if missing.size:
@@ -379,6 +578,8 @@ class MultilevelPreconditioner:
             self._code, self._coarse_code = compile_rigid_kernels(K.gdim)
         else:
             self._code = self._coarse_code = compile_kernels(K.gdim)
+        if seam.free:
+            seam.build(self._levels)
         self._on = {}  # device index -> _OnDevice
 
     # ---- what was asked for (read-only) ----------------------------------------------------------------------------------------
@@ -452,6 +653,9 @@ class MultilevelPreconditioner:
         if self._rigid:  # the three transfer kernels of the pair (D, Dc), and under "coarse" every kernel of the coarse program by its name
             r.update({"rigid_" + kernel[len("fcamd_mr_"): -len("_kernel")]: kernel_resources(self._code.log, kernel) for kernel in RIGID_KERNELS})
             r["coarse"] = {kernel: kernel_resources(self._coarse_code.log, kernel) for kernel in solver.KERNELS + KERNELS + RIGID_KERNELS}
+        if self._seam.free:  # the two kernels of the first Galerkin step of an operator
+            r["free_galerkin"] = kernel_resources(self._seam.gather_code.log, FREE_GALERKIN_KERNEL)
+            r["free_element"] = kernel_resources(self._seam.element_code.log, _matrix.ELEMENT_KERNEL)
         return r
 
     @property
@@ -507,8 +711,11 @@ class MultilevelPreconditioner:
     def _setup(self, dev: int, values, control) -> None:
         """the Galerkin values of every coarse level, then the inverses of every level's own blocks (asynchronous)"""
         on, cap, dd = self._device(dev), BLOCKS_PER_CU * jit.num_cu(dev), self.K.gdim**2
-        tables = self.K._tables(dev)
+        tables = None if self._seam.free else self.K._tables(dev)
         for l, lv in enumerate(self._levels[:-1]):
+            if l == 0 and self._seam.free:  # no values to fold: level 1 straight from the element matrices
+                self._seam.galerkin(self, dev, values, cap)
+                continue
             if self._rigid:
                 a, t = RigidArgs(), on.tables[l]
                 a.fine_values = (values if l == 0 else on.values[l]).data_ptr()
@@ -530,8 +737,10 @@ class MultilevelPreconditioner:
             a.n_coarse = dd * self._levels[l + 1].nnzb
             jit.launch(self._code, dev, self._blocks(a.n_coarse, cap), a, "MultilevelPreconditioner Galerkin launch", kernel=GALERKIN_KERNEL)
         for l, lv in enumerate(self._levels):
-            jit.launch(self._program(l), dev, self._blocks(lv.n_nodes, cap), self._level_args(dev, l, values, control), "MultilevelPreconditioner inverse launch",
-                       kernel=solver.INVERSE_KERNEL)
+            a = self._level_args(dev, l, values, control)
+            if l == 0:  # (a matrix: its values; an operator: the block array its diagonal kernels fill here)
+                a.values = self._seam.blocks(self, dev, values)
+            jit.launch(self._program(l), dev, self._blocks(lv.n_nodes, cap), a, "MultilevelPreconditioner inverse launch", kernel=solver.INVERSE_KERNEL)
 
     def _plan(self, dev: int, values, control, r_ptr: int, z_ptr: int) -> list:
         """the launches of one application ``z = M^-1 r``: ``[(code, kernel, blocks, args, what)]``"""
@@ -546,6 +755,9 @@ class MultilevelPreconditioner:
         ops = []
 
         def product(l):
+            if l == 0:  # one launch of the matrix-vector kernel, or the operator's two
+                ops.extend(self._seam.product(self, dev, values, control, x_of[0], q_of[0], cap))
+                return
             a = self._level_args(dev, l, values, control)
             a.va, a.q, a.mode = x_of[l], q_of[l], _MODE_QUIET
             ops.append((self._program(l), solver.MATVEC_KERNEL, max(1, min(int(a.nseg), cap)), a, "MultilevelPreconditioner matrix-vector launch"))
@@ -608,7 +820,7 @@ class MultilevelPreconditioner:
         # partial sums, the vectors, the mask and the level-0 tables.  The control and the mask are kept alive with the plan, so
         # that their addresses cannot be handed to other tensors while it is cached.
         key = (values.data_ptr(), control.device_block.data_ptr(), control.partials.data_ptr(), r_ptr, z_ptr, None if mask is None else mask.data_ptr(),
-               tuple(t.data_ptr() for t in self._op.tables(dev)), jit.num_cu(dev), self._coarse_space)
+               self._seam.key(self, dev), jit.num_cu(dev), self._coarse_space)
         have = on.plans.pop(key, None)  # (taken out and put back: the dict keeps the order of the last use)
         if have is None:
             have = (self._plan(dev, values, control, r_ptr, z_ptr), (control, mask))
@@ -640,7 +852,7 @@ class MultilevelPreconditioner:
         import torch
 
         dev = self.device
-        self.K._check("values", values, self.K.nnz, dev)
+        self._seam.check(values, dev)
         with torch.cuda.device(dev):
             if self.K.shape[0]:
                 self._setup(dev, values, self._own_control(dev))
@@ -653,7 +865,7 @@ class MultilevelPreconditioner:
         import torch
 
         dev, n = self.device, self.K.shape[0]
-        self.K._check("values", values, self.K.nnz, dev)
+        self._seam.check(values, dev)
         self.K._check("r", r, n, dev)
         if out is not None:
             self.K._check("out", out, n, dev)

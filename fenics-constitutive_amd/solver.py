@@ -52,8 +52,10 @@ honours the status and touches neither ``pq`` nor the counter.
 tangent of the quadrature points: ``cg(tangent, b, x0=None, out=None)``.  The product and ``p . q`` come from the operator's two kernels
 through the same seam (``_FreeOperator`` in ``_Operator``'s place; the same control block, modes and ordered dot), block-Jacobi from the
 operator's diagonal-block kernels followed by THIS module's inverse kernel on the block array -- a BSR values array whose diagonal
-table is ``0 .. n-1`` --, and the start, update and direction kernels are used as they are.  The multilevel preconditioner needs the
-matrix and is refused.
+table is ``0 .. n-1`` --, and the start, update and direction kernels are used as they are.  The multilevel preconditioner is an
+instance built on the same operator, ``MultilevelPreconditioner(A)`` (program ``FCAMD_CG_PRECOND = 2`` as with a matrix): it needs no
+fine matrix, its first coarse level is gathered from the element matrices (``multilevel.py``).  The string form "multilevel" builds
+the preconditioner of a matrix and stays refused with an operator.
 
 LDS of a block: ``lds_bytes(kernel)``; the same ``LDS_CAP`` as the other operators.
 """
@@ -425,9 +427,9 @@ class ConjugateGradient:
     and norms back, so the stream has been waited for when it returns.  Use an object from one stream at a time.
 
     ``K`` may be a ``TangentOperator`` instead: the call is then ``cg(tangent, b, x0=None, out=None)`` with the ``S*S n_points`` tangent a law
-    wrote in the values' place, ``preconditioner`` is "block_jacobi" or ``None`` ("multilevel" or a ``MultilevelPreconditioner``: a
-    ``ValueError``, its Galerkin values need the matrix), and a node that belongs to no cell is refused at construction as a missing
-    diagonal block is.  Everything else -- ``x0``, ``check_every``, the statuses, ``SolveResult`` and its ``looks`` -- is the same."""
+    wrote in the values' place, ``preconditioner`` is "block_jacobi", ``None`` or a ``MultilevelPreconditioner`` built on this very operator
+    (translations only; the string "multilevel", or an instance built on another object: a ``ValueError``), and a node that belongs to
+    no cell is refused at construction as a missing diagonal block is.  Everything else -- ``x0``, ``check_every``, the statuses, ``SolveResult`` and its ``looks`` -- is the same."""
 
     def __init__(self, K: TangentMatrix, preconditioner="block_jacobi", rtol: float = 1e-8, atol: float = 0.0, maxiter: int | None = None,
                  check_every: int = 16):
@@ -436,9 +438,12 @@ class ConjugateGradient:
             raise TypeError(f"K must be a TangentMatrix, got {type(K).__name__}")
         from .multilevel import MultilevelPreconditioner
 
-        if free and ((isinstance(preconditioner, str) and preconditioner == "multilevel") or isinstance(preconditioner, MultilevelPreconditioner)):
-            raise ValueError("the multilevel preconditioner needs the matrix (its Galerkin values are formed from the values array): with a "
-                             f"TangentOperator the preconditioner must be one of {PRECONDITIONERS}")
+        if free and isinstance(preconditioner, str) and preconditioner == "multilevel":
+            raise ValueError('preconditioner="multilevel" builds the multilevel preconditioner of a matrix: with a TangentOperator A pass the instance, '
+                             f"MultilevelPreconditioner(A), or one of {PRECONDITIONERS}")
+        if free and isinstance(preconditioner, MultilevelPreconditioner) and preconditioner.K is not K:
+            raise ValueError("the MultilevelPreconditioner was built for another object: the multilevel preconditioner of a TangentOperator A is "
+                             "MultilevelPreconditioner(A), built on this very operator")
         if isinstance(preconditioner, str) and preconditioner == "multilevel":
             pass  # built below, once everything else has been validated
         elif isinstance(preconditioner, MultilevelPreconditioner):
@@ -561,9 +566,9 @@ class ConjugateGradient:
             a.has_x0 = 0 if x0 is None else 1
             cap = BLOCKS_PER_CU * jit.num_cu(dev)
             ml = self._ml
-            if free and self.preconditioner:  # the nodes' own blocks without a matrix: a BSR values array over the diagonal pattern
+            if free and self.preconditioner and ml is None:  # the nodes' own blocks without a matrix: a BSR values array over the diagonal pattern
                 a.values = K.diagonal_blocks(values, out=self._diagonal_blocks(dev)).data_ptr()
-            if ml is not None:
+            if ml is not None:  # (on an operator ``values`` is the tangent: the preconditioner forms the blocks and level 1 from it)
                 ml._setup(dev, values, control)
             elif self.preconditioner:
                 jit.launch(self._code, dev, max(1, min(-(-K.n_nodes // 256), cap)), a, "ConjugateGradient inverse launch", kernel=INVERSE_KERNEL)

@@ -264,6 +264,12 @@ class TangentOperator:
         """both launches of ``out = A v`` on pointers that have been validated (the solver's seam); ``mode``: ``MODE_QUIET`` -- the
         product alone --, ``MODE_PLAIN`` -- the ordered ``v . out`` into the control block's ``dot`` --, ``MODE_ITERATE`` -- into ``pq``, under
         the status"""
+        for code, kernel, blocks, args, what in self._launches(dev, tangent_ptr, v_ptr, out_ptr, mode, partials_ptr, control_ptr):
+            jit.launch(code, dev, blocks, args, what, kernel=kernel)
+
+    def _launches(self, dev: int, tangent_ptr: int, v_ptr: int, out_ptr: int, mode: int, partials_ptr: int = 0, control_ptr: int = 0) -> list:
+        """the launches of ``_apply`` as ``[(code, kernel, blocks, args, what)]``, for a caller that keeps them (the launch plan of the
+        multilevel preconditioner): they hold the pointers given here, those of ``force``'s tables and element forces and the mask's"""
         import torch
 
         force, op = self.force, self.op
@@ -273,6 +279,7 @@ class TangentOperator:
         mask_ptr = 0 if mask is None else mask.data_ptr()
         cap = BLOCKS_PER_CU * jit.num_cu(dev)
         fe_ptr = 0
+        ops = []
         if self.n_cells:
             dofmap, ref, jinv, _ = op._tables(dev)
             weights = force._tables(dev)[0]
@@ -283,10 +290,11 @@ class TangentOperator:
             tiles = -(-self.n_cells // cells_per_tile(self.gdim, self.points_per_cell))
             ea = ElementArgs(tangent_ptr, v_ptr, dofmap.data_ptr(), mask_ptr, ref.data_ptr(), jinv.data_ptr(), weights.data_ptr(), fe_ptr,
                              control_ptr, self.n_cells, mode, 0)
-            jit.launch(self._code, dev, min((tiles + 3) // 4, cap), ea, "TangentOperator element launch")  # a wave per tile, 4 waves per block
+            ops.append((self._code, None, min((tiles + 3) // 4, cap), ea, "TangentOperator element launch"))  # a wave per tile, 4 waves per block
         nseg = -(-nd // SEG)
         na = NodeArgs(fe_ptr, node_ptr.data_ptr(), adj.data_ptr(), v_ptr, mask_ptr, out_ptr, partials_ptr, control_ptr, nd, nseg, mode, 0)
-        jit.launch(self._code, dev, max(1, min(nseg, cap)), na, "TangentOperator node launch", kernel=NODE_KERNEL)  # a block per segment
+        ops.append((self._code, NODE_KERNEL, max(1, min(nseg, cap)), na, "TangentOperator node launch"))  # a block per segment
+        return ops
 
     def __call__(self, tangent, v, out=None):
         """``y = M K M v + (I - M) v`` for this tangent (asynchronous, on torch's current stream)"""
