@@ -2,24 +2,122 @@
 csrc/jit/tangent_operator.hip composed from the oracles the operator's arithmetic is made of -- gradient_util.oracle (the
 producer), force_util.tangent_action_oracle (the tangent form of the force operator), matrix_util.element_matrices (the diagonal
 blocks) and solver_util.ordered_dot --, the conjugate gradients of solver_util on a product callable, inputs whose cells name
-distinct nodes, and the Newton loop of examples/cube_tension_matrix_free_solve.py on the CPU."""
+distinct nodes, and the Newton loop of examples/cube_tension_matrix_free_solve.py on the CPU; the shapes that reach every compile-time
+branch of the template, its constants restated from the header comment, and a dense stiffness in np.longdouble written out from
+K = sum_p w_p B_p^T C_p B_p that shares no code with the ordered oracles."""
 
 from types import SimpleNamespace
 
 import numpy as np
 
-from force_util import MANDEL_DIM, chain_length, max_valence, random_inputs, tangent_action_oracle
+from force_util import H, MANDEL_DIM, PAIRS, chain_length, max_valence, n_pairs, random_inputs, tangent_action_oracle
 from gradient_util import EPS, SHAPES, _terms, oracle
 from matrix_util import element_matrices
 from solver_util import apply_inverse, block_inverses, ordered_dot
+
+
+#: name -> (D, A, Q, the natural form of the inverse Jacobians is per cell): the four shapes the operator's tests began with and one
+#: for every branch the template of csrc/jit/tangent_operator.hip chooses at compile time (``tiling_constants`` names them;
+#: test_tangent_operator.py asserts that each is reached)
+TILING_SHAPES = {
+    "hex8": SHAPES["hex8"],
+    "tet_p2": SHAPES["tet_p2"],
+    "tri_p2": SHAPES["tri_p2"],
+    "interval": SHAPES["interval"],
+    "q3": (3, 4, 3, True),  # W = 20 = 64 // 3 - 1; diagonal slab 11 (affine) and 9 (per point)
+    "q3_1d": (1, 2, 3, True),  # W = 20 with D = 1 and S*S = 1: odd element counts at the ends of the tiles
+    "q5": SHAPES["q5"],  # W = 12: whole tiles of 60 points, four dead lanes
+    "tet_p1": SHAPES["tet_p1"],  # W = 64 with Q = 1 in 3-D
+    "q7_2d": (2, 3, 7, True),  # W = 9: 63 points; CW = 21: 63 live lanes of the diagonal blocks
+    "odd33_1d": (1, 2, 33, False),  # W = 1, kEven false: every second tile starts off the 16-byte grid
+    "odd33_3d": (3, 4, 33, False),  # the same with S*S = 36 and D*D = 9: the guarded loads of the per-point jinv
+    "wide": (3, 22, 2, True),  # CW = 2: 20 dead lanes; diagonal slab 5
+    "wide64": (3, 64, 1, True),  # CW = 1 through A >= 64, one pass, diagonal slab 2, the register budget of two waves
+    "wide70": (3, 70, 2, True),  # two passes over the nodes, the second ragged at 6 of 64 lanes
+    "wide130": (3, 130, 1, True),  # three passes, diagonal slab 1
+}
+#: the shapes whose element matrix TangentMatrix refuses (and MultilevelPreconditioner with it): nothing assembled to compare with
+NO_MATRIX = ("wide64", "wide70", "wide130")
+
+
+def tiling_constants(d_, a_, q_, affine):
+    """the compile-time constants of csrc/jit/tangent_operator.hip restated from its header comment: ``W`` cells and ``kPts`` points
+    of a whole product tile, ``kEven`` (whole tiles start on the 16-byte grid), the ``product_slab`` points whose tangent rows pass
+    through a wave's region of 64 * D*D doubles at a time, ``CW`` cells of a diagonal-block tile, ``kPasses`` over the nodes, and the
+    ``diagonal_slab``: the most points, up to 16, whose tangent rows, per-point inverse Jacobians, A*D basis gradients and weights fit
+    the region, every part padded to an even count"""
+    dd, ss = d_ * d_, MANDEL_DIM[d_] ** 2
+    region = 64 * dd
+    w0 = 64 // q_
+    w = w0 - 1 if w0 > 1 and (w0 * q_ * dd) % 2 else w0
+    product_slab = region // ss // 2 if d_ == 3 else region // ss
+
+    def even(n):
+        return n + (n & 1)
+
+    def fits(slab):
+        return even(slab * ss) + (0 if affine else even(slab * dd)) + even(slab * a_ * d_) + even(slab) <= region
+
+    return SimpleNamespace(W=w, kPts=w * q_, kEven=(w * q_ * dd) % 2 == 0, product_slab=product_slab, CW=1 if a_ >= 64 else 64 // a_,
+                           kPasses=-(-a_ // 64), diagonal_slab=max((s for s in range(1, 17) if fits(s)), default=0))
+
+
+def strain_matrix(g, d_):
+    """the Mandel B of one point, [S][A*D] in np.longdouble, from its basis gradients g[a][x]: row i < D holds g[a][i] in column
+    (a, i); the row of the m-th pair (i, j) holds H * g[a][j] in column (a, i) and H * g[a][i] in column (a, j); the zz row of D = 2
+    stays zero"""
+    a_ = g.shape[0]
+    b = np.zeros((MANDEL_DIM[d_], a_ * d_), dtype=np.longdouble)
+    h = np.longdouble(H)
+    for a in range(a_):
+        for i in range(d_):
+            b[i, a * d_ + i] = g[a, i]
+        for m in range(n_pairs(d_)):
+            i, j = PAIRS[m]
+            b[3 + m, a * d_ + i] = h * g[a, j]
+            b[3 + m, a * d_ + j] = h * g[a, i]
+    return b
+
+
+def dense_stiffness(tables, tangent, mask=None):
+    """K = sum_p w_p B_p^T C_p B_p as a dense [D n_nodes][D n_nodes] np.longdouble, written out from the definition and sharing no
+    code with the ordered oracles: per point the basis gradients g = ref[q] jinv, the Mandel B of ``strain_matrix``, the point's
+    S x S tangent, the weight; the cell's sum scattered through the dofmap.  ``mask``: rows and columns of the constrained dofs are
+    the identity's"""
+    dofmap, ref, jinv, weights, n_nodes = tables
+    ld = np.longdouble
+    q_, a_, d_ = ref.shape
+    s_ = MANDEL_DIM[d_]
+    cmat = np.asarray(tangent, dtype=np.float64).reshape(dofmap.shape[0], q_, s_, s_).astype(ld)
+    refl = ref.astype(ld)
+    k = np.zeros((d_ * n_nodes, d_ * n_nodes), dtype=ld)
+    for c, nodes in enumerate(dofmap):
+        ke = np.zeros((a_ * d_, a_ * d_), dtype=ld)
+        for q in range(q_):
+            j = (jinv[c, q] if jinv.ndim == 4 else jinv[c]).astype(ld)
+            b = strain_matrix(refl[q] @ j, d_)
+            ke += ld(weights[c, q]) * (b.T @ cmat[c, q] @ b)
+        dofs = (d_ * nodes.astype(np.int64)[:, None] + np.arange(d_)[None, :]).reshape(-1)
+        k[np.ix_(dofs, dofs)] += ke  # (the nodes of a cell are distinct: every entry once)
+    if mask is not None:
+        k[mask, :] = 0
+        k[:, mask] = 0
+        k[mask, mask] = 1
+    return k
+
+
+def dense_diagonal_blocks(k, n_nodes, d_):
+    """[n_nodes][D][D]: the nodes' own blocks of a dense matrix"""
+    return np.stack([k[d_ * v: d_ * v + d_, d_ * v: d_ * v + d_] for v in range(n_nodes)])
 
 
 def distinct_inputs(shape, n_cells, seed, integer, affine, every_node=False):
     """force_util.random_inputs with a dofmap whose cells name distinct nodes (the operator refuses others): every cell a random
     choice of A of the nodes; node 0 and the last node stay in use, node ``lonely`` in the middle of the numbering is in no cell.
     ``every_node``: the nodes are renumbered so that every one is in a cell (``lonely`` is None): a system one can solve"""
+    shape = TILING_SHAPES[shape] if isinstance(shape, str) else shape
     t = random_inputs(shape, n_cells, seed, integer, affine)
-    d_, a_, q_, _ = SHAPES[shape] if isinstance(shape, str) else shape
+    d_, a_, q_, _ = shape
     n_used = t["n_nodes"] - 1
     rng = np.random.default_rng(seed + 2000)
     dofmap = np.stack([rng.permutation(n_used)[:a_] for _ in range(n_cells)]).astype(np.int32)
@@ -70,10 +168,11 @@ def product_chain_length(dofmap, ref, n_nodes, row_blocks):
     return (a_ + d_ + 2) + 2 * chain_length(d_, q_, valence, True) + d_ * row_blocks + 2
 
 
-def diagonal_blocks_oracle(tangent, dofmap, ref, jinv, weights, n_nodes, mask=None, chunk_cells=None):
+def diagonal_blocks_oracle(tangent, dofmap, ref, jinv, weights, n_nodes, mask=None, chunk_cells=None, absolute=False):
     """what TangentOperator.diagonal_blocks computes, on the bits: de[c][a] = ke[c][a][.][a][.] of matrix_util.element_matrices, added
     per node in ascending c*A + a, the cells in ascending chunks (a later chunk goes on from what is there); an entry whose row or
-    column dof is constrained is the constant 1.0 (diagonal) or 0.0"""
+    column dof is constrained is the constant 1.0 (diagonal) or 0.0 (``absolute``: every factor replaced by its absolute value -- the S
+    of the rounding bound)"""
     c_, a_ = dofmap.shape
     d_ = ref.shape[2]
     s_ = MANDEL_DIM[d_]
@@ -83,7 +182,7 @@ def diagonal_blocks_oracle(tangent, dofmap, ref, jinv, weights, n_nodes, mask=No
     cmat = np.asarray(tangent, dtype=np.float64).reshape(c_, q_ * s_ * s_)
     for c0 in range(0, c_, chunk_cells):
         c1 = min(c0 + chunk_cells, c_)
-        ke = element_matrices(cmat[c0:c1].reshape(-1), ref, jinv[c0:c1], weights[c0:c1])
+        ke = element_matrices(cmat[c0:c1].reshape(-1), ref, jinv[c0:c1], weights[c0:c1], absolute)
         de = np.stack([ke[:, a, :, a, :] for a in range(a_)], axis=1).reshape(-1, d_, d_)  # [c*A + a][r][s]
         flat = dofmap[c0:c1].reshape(-1)
         order = np.argsort(flat, kind="stable")
@@ -184,5 +283,6 @@ def oracle_free_loop(state, dofmap, ref, jinv, weights, n_nodes, **cg_options):
     return loop
 
 
-__all__ = ["EPS", "conjugate_gradient", "diagonal_blocks_oracle", "distinct_inputs", "operator_solve", "oracle_free_loop", "product_chain_length",
-           "product_oracle", "random_mask"]
+__all__ = ["EPS", "NO_MATRIX", "TILING_SHAPES", "conjugate_gradient", "dense_diagonal_blocks", "dense_stiffness", "diagonal_blocks_oracle",
+           "distinct_inputs", "operator_solve", "oracle_free_loop", "product_chain_length", "product_oracle", "random_mask", "strain_matrix",
+           "tiling_constants"]

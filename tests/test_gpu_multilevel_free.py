@@ -3,7 +3,8 @@ TangentOperator, csrc/jit/multilevel_free.hip): the values of every coarse level
 cycles and whole conjugate-gradient runs compared ON THE BITS with the NumPy oracle of multilevel_free_util.py -- for every scratch
 size, on hierarchies of one, two and three levels, under a grid capped at one compute unit, for every ``check_every`` --, the
 statuses and refusals, the assembled route and block-Jacobi untouched next to it, and the Newton loop of
-examples/cube_tension_matrix_free_multilevel.py.  Every output a caller hands in lies between canaries."""
+examples/cube_tension_matrix_free_multilevel.py.  Every output a caller hands in lies between canaries.  The setup also runs at
+``q3``, ``q5`` and ``wide`` of tangent_operator_util.TILING_SHAPES: A = 4 with tiles of 20 and 12 cells, and A*D = 66 columns."""
 
 import os
 import sys
@@ -25,10 +26,11 @@ from fenics_constitutive_amd import gradient, jit, matrix, multilevel, solver  #
 from fenics_constitutive_amd import tangent_operator as to  # noqa: E402
 from fenics_constitutive_amd.hostio import to_device, to_host  # noqa: E402
 from force_util import MANDEL_DIM, cell_counts  # noqa: E402
-from gradient_util import SHAPES, cube_operator_tables  # noqa: E402
+from gradient_util import cube_operator_tables  # noqa: E402
 import multilevel_free_util as MF  # noqa: E402
 import multilevel_util as MU  # noqa: E402
 from solver_util import SEG, from_format, spd_tangent  # noqa: E402
+from tangent_operator_util import TILING_SHAPES as SHAPES  # noqa: E402
 from tangent_operator_util import distinct_inputs, operator_solve, random_mask  # noqa: E402
 
 MARGIN = 64  # doubles on either side of an output (a multiple of two: the output stays on the 16-byte grid)
@@ -94,7 +96,7 @@ def status_of(pc):
 # 1. setup: the values of every coarse level and the nodes' own blocks
 # ---------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("affine", [True, False], ids=["affine", "per_point"])
-@pytest.mark.parametrize("shape", ML_SHAPES)
+@pytest.mark.parametrize("shape", ML_SHAPES + ("q3", "q5", "wide"))
 def test_setup_on_the_bits(shape, affine):
     d_, a_, q_, _ = SHAPES[shape]
     cw = matrix.cells_per_tile(d_, a_)

@@ -2,7 +2,9 @@
 product, its fused ordered dot, the diagonal blocks and whole conjugate-gradient runs compared ON THE BITS with the NumPy oracle of
 tangent_operator_util.py and with the routes the package already has -- ``tangent_action(op(.))`` in both gradient layouts,
 ``K.diagonal_blocks(K(tangent))`` --, every output between canaries; the statuses, the refusals, and the Newton loop of
-examples/cube_tension_matrix_free_solve.py."""
+examples/cube_tension_matrix_free_solve.py.  The product and the diagonal blocks run at every tiling the template generates
+(tangent_operator_util.TILING_SHAPES: W one less than 64 // Q, tiles off the 16-byte grid, dead lanes, A >= 64 with one, two and three
+passes over the nodes, every slab size), the grid-stride loops of both element kernels under the cap of one compute unit."""
 
 import os
 import sys
@@ -26,13 +28,17 @@ from fenics_constitutive_amd import tangent_operator as to  # noqa: E402
 from fenics_constitutive_amd.hostio import to_device, to_host  # noqa: E402
 from fenics_constitutive_amd.resident import ResidentState  # noqa: E402
 from force_util import MANDEL_DIM, cell_counts  # noqa: E402
-from gradient_util import SHAPES, cube_operator_tables  # noqa: E402
+from gradient_util import cube_operator_tables  # noqa: E402
 from solver_util import SEG, conjugate_gradient, ordered_dot, spd_tangent  # noqa: E402
-from tangent_operator_util import diagonal_blocks_oracle, distinct_inputs, operator_solve, product_oracle, random_mask  # noqa: E402
+from tangent_operator_util import (NO_MATRIX, TILING_SHAPES, diagonal_blocks_oracle, distinct_inputs, operator_solve, product_oracle,  # noqa: E402
+                                   random_mask, tiling_constants)
 
 MARGIN = 64  # doubles on either side of an output (a multiple of two: the output stays on the 16-byte grid)
 CANARY = np.uint64(0x7FF8DEADBEEF0BAD)  # a NaN no arithmetic produces
 TO_SHAPES = ("hex8", "tet_p2", "tri_p2", "interval")
+SHAPES = TILING_SHAPES  # every tiling the template generates (tangent_operator_util.py; test_tangent_operator.py: each branch is reached)
+PRODUCT_SHAPES = tuple(name for name in TILING_SHAPES if name != "wide130")
+SOLVE_SHAPES = TO_SHAPES + ("q3", "odd33_3d", "wide70")
 VM_P = {"p_ka": 175000.0, "p_mu": 80769.0, "p_y0": 1200.0, "p_y00": 2500.0, "p_w": 200.0}
 
 
@@ -107,10 +113,11 @@ def check_product(a, t, tangent, v, mask, what, pairs=()):
 
 
 @pytest.mark.parametrize("affine", [True, False], ids=["affine", "per_point"])
-@pytest.mark.parametrize("shape", TO_SHAPES)
+@pytest.mark.parametrize("shape", PRODUCT_SHAPES)
 def test_product_on_the_bits(shape, affine):
     d_, a_, q_, _ = SHAPES[shape]
     w = force_module.cells_per_tile(d_, q_)
+    assert w == tiling_constants(d_, a_, q_, affine).W
     for n_cells in cell_counts(w, q_):
         integer = n_cells % 2 == 0
         t = distinct_inputs(shape, n_cells, 7 + n_cells, integer, affine)
@@ -125,7 +132,9 @@ def test_product_on_the_bits(shape, affine):
             assert (bits(have.reshape(-1, d_)[t["lonely"]]) == 0).all(), what  # the node in no cell: +0.0
             if mask is not None:
                 assert mask.any() and np.array_equal(bits(have[mask]), bits(v[mask])), what
-                assert np.abs(have[~mask]).max() > 0 or n_cells == 1, what
+                used = np.repeat(np.bincount(t["dofmap"].reshape(-1), minlength=t["n_nodes"]) > 0, d_)
+                assert (used & ~mask).any() == (n_cells > 1) or w == 1, what  # (one cell: all of its dofs are constrained)
+                assert np.abs(have[~mask]).max() > 0 or not (used & ~mask).any(), what
     assert a(to_device(t["tangent"], "cuda"), to_device(v, "cuda")).shape == (a.shape[0],)  # without out: a new tensor
 
 
@@ -208,20 +217,27 @@ def test_dot_on_one_compute_unit(one_cu):
 # 3. the diagonal blocks
 # ---------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("affine", [True, False], ids=["affine", "per_point"])
-@pytest.mark.parametrize("shape", TO_SHAPES)
+@pytest.mark.parametrize("shape", tuple(TILING_SHAPES))
 def test_diagonal_blocks_on_the_bits(shape, affine):
     d_, a_, q_, _ = SHAPES[shape]
     cw = to.diagonal_cells_per_tile(a_)
+    assert cw == tiling_constants(d_, a_, q_, affine).CW
     n_cells = 3 * cw + 1
     t = distinct_inputs(shape, n_cells, 13, False, affine)
     op, f = operators(t)
     tangent = to_device(t["tangent"], "cuda")
     tile = cw * a_ * d_ * d_ * 8
     for mask in (None, random_mask(t, d_, 4, whole_cell=1)):
-        k = fc.TangentMatrix(f)
-        k.set_constrained(mask)
-        want = to_host(k.diagonal_blocks(k(tangent)))
-        assert_same_bits(want, diagonal_blocks_oracle(t["tangent"], *tables_of(t), mask=mask), f"{shape}: the oracle and the matrix")
+        want = diagonal_blocks_oracle(t["tangent"], *tables_of(t), mask=mask)
+        if shape in NO_MATRIX:  # no assembled matrix to stand between: the oracle alone (test_tangent_operator.py ties it to the dense K)
+            with pytest.raises(ValueError, match="does not compile without scratch"):
+                fc.TangentMatrix(f)
+        else:
+            k = fc.TangentMatrix(f)
+            k.set_constrained(mask)
+            have = to_host(k.diagonal_blocks(k(tangent)))
+            assert_same_bits(have, want, f"{shape}: the oracle and the matrix")
+            want = have
         for scratch in (tile, 2 * tile + 8, None):  # one tile of cells, two, everything
             a = fc.TangentOperator(f, scratch_bytes=scratch)
             a.set_constrained(mask)
@@ -230,9 +246,48 @@ def test_diagonal_blocks_on_the_bits(shape, affine):
             a.diagonal_blocks(tangent, out=out)
             torch.cuda.synchronize()
             assert_margins_intact(buf, d_ * d_ * t["n_nodes"])
-            assert_same_bits(to_host(out), want, f"{shape} affine={affine} scratch={scratch} mask={'yes' if mask is not None else 'no'}")
+            assert_same_bits(to_host(out), want, f"{shape} affine={affine} cells={n_cells} scratch={scratch} mask={'yes' if mask is not None else 'no'}")
         assert a.diagonal_blocks(tangent).shape == (t["n_nodes"], d_, d_)
     assert (bits(want.reshape(-1, d_, d_)[t["lonely"]]) == 0).all() and np.abs(want).max() > 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 3b. the grid-stride loops under the cap of one compute unit: more than two trips, the ragged tile last
+# ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape,n_cells", [("q3", 129 * 20 + 7), ("odd33_3d", 130)])
+def test_product_on_one_compute_unit(shape, n_cells, one_cu):
+    d_, a_, q_, affine = SHAPES[shape]
+    k = tiling_constants(d_, a_, q_, affine)
+    tiles = -(-n_cells // k.W)
+    assert tiles > 2 * gradient.BLOCKS_PER_CU * 4 and (n_cells % k.W != 0) == (k.W > 1)  # (four waves, a tile each, per block)
+    t = distinct_inputs(shape, n_cells, 31, False, affine)
+    a = fc.TangentOperator(operators(t)[1])
+    v = np.random.default_rng(n_cells).normal(size=a.shape[0])
+    for mask in (None, random_mask(t, d_, 6, whole_cell=n_cells - 1)):
+        del one_cu[:]
+        check_product(a, t, t["tangent"], v, mask, f"{shape} affine={affine} cells={n_cells} on one compute unit mask={'yes' if mask is not None else 'no'}")
+        assert (to.ELEMENT_KERNEL, gradient.BLOCKS_PER_CU) in one_cu  # the launch really was capped
+
+
+def test_diagonal_blocks_on_one_compute_unit(one_cu):
+    shape, n_cells = "wide70", 129
+    d_, a_, q_, affine = SHAPES[shape]
+    k = tiling_constants(d_, a_, q_, affine)
+    assert k.kPasses == 2 and -(-n_cells // k.CW) > 2 * gradient.BLOCKS_PER_CU * 4
+    t = distinct_inputs(shape, n_cells, 33, False, affine)
+    a = fc.TangentOperator(operators(t)[1])
+    tangent = to_device(t["tangent"], "cuda")
+    for mask in (None, random_mask(t, d_, 8, whole_cell=n_cells - 1)):
+        a.set_constrained(mask)
+        assert len(a.chunks()) == 1
+        del one_cu[:]
+        buf, out = guarded(d_ * d_ * t["n_nodes"])
+        a.diagonal_blocks(tangent, out=out)
+        torch.cuda.synchronize()
+        assert_margins_intact(buf, d_ * d_ * t["n_nodes"])
+        assert_same_bits(to_host(out), diagonal_blocks_oracle(t["tangent"], *tables_of(t), mask=mask),
+                         f"{shape} cells={n_cells} on one compute unit mask={'yes' if mask is not None else 'no'}")
+        assert (to.DIAGONAL_ELEMENT_KERNEL, gradient.BLOCKS_PER_CU) in one_cu and (to.DIAGONAL_NODE_KERNEL, gradient.BLOCKS_PER_CU) in one_cu
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -254,10 +309,12 @@ def assert_same_result(res, x, want, what):
     assert bits(np.float64(res.rhs_norm)) == bits(np.float64(want.rhs_norm)), what
 
 
-@pytest.mark.parametrize("shape", TO_SHAPES)
+@pytest.mark.parametrize("shape", SOLVE_SHAPES)
 def test_exactly_k_iterations(shape):
     d_, a_, q_, affine = SHAPES[shape]
     n_cells = -(-257 // q_)
+    if shape == "wide70":  # the fewest cells with two tiles of the product (W = 32) and two of the diagonal blocks (CW = 1)
+        n_cells = force_module.cells_per_tile(d_, q_) + 1
     t = distinct_inputs(shape, n_cells, 21, False, affine, every_node=True)
     a = fc.TangentOperator(operators(t)[1])
     mask = random_mask(t, d_, 26)
