@@ -43,6 +43,9 @@ preconditioner, its cycle's launches before either product (``p -> y``, ``s -> z
 launch, no grid-wide barrier, no kernel that waits on a flag.
 
 LDS of a block: ``lds_bytes(kernel, preconditioner)``.
+
+``BiCGStab`` takes a ``TangentMatrix`` only.  The same recurrence on a matrix-free ``TangentOperator`` -- this module's start, half-step,
+full-step and direction kernels around the operator's own product -- is ``bicgstab_free.MatrixFreeBiCGStab``.
 """
 
 from __future__ import annotations

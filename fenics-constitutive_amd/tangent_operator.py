@@ -27,6 +27,9 @@ twice is refused.
 
 LDS of a block of either element kernel (``lds_bytes``): that of the force operator -- the reference table and four regions of
 ``64 * D*D`` doubles; the same ``LDS_CAP``.  ``Q`` may be at most 64.
+
+For a tangent that is not symmetric the operator goes under ``bicgstab_free.MatrixFreeBiCGStab``: the element kernel as it stands and a
+node kernel of that module's own program (``csrc/jit/bicgstab_free.hip``) that leaves BiCGStab's dots behind the product.
 """
 
 from __future__ import annotations

@@ -14,8 +14,9 @@ from ._api import *  # noqa: E402,F401,F403
 from ._api import __all__ as _api_all  # noqa: E402
 from ._api import __version__  # noqa: E402,F401
 from .bicgstab import BiCGStab  # noqa: E402,F401
+from .bicgstab_free import MatrixFreeBiCGStab  # noqa: E402,F401
 from .multilevel import MultilevelPreconditioner  # noqa: E402,F401
 from .solver import ConjugateGradient  # noqa: E402,F401
 from .tangent_operator import TangentOperator  # noqa: E402,F401
 
-__all__ = [*_api_all, "BiCGStab", "ConjugateGradient", "MultilevelPreconditioner", "TangentOperator"]
+__all__ = [*_api_all, "BiCGStab", "ConjugateGradient", "MatrixFreeBiCGStab", "MultilevelPreconditioner", "TangentOperator"]
