@@ -59,8 +59,8 @@ sizes.  Two programs per object: the fine one (``FCAMD_CG_D = D``, the object's 
 coarse one (``FCAMD_CG_D = Dc``: every level ``l >= 1`` and the ``(Dc, Dc)`` transfer kernels).  A level-0 aggregate whose columns of ``P``
 are linearly dependent -- a lone node, all members at one point, in 3-D all members on one line -- is refused at construction.
 
-*On a matrix-free operator* (``MultilevelPreconditioner(A)`` with a ``TangentOperator``; csrc/jit/multilevel_free.hip; translations
-only).  The hierarchy is that of ``matrix.block_pattern(dofmap, n_nodes)``: every table is the one of a ``TangentMatrix`` of the same
+*On a matrix-free operator* (``MultilevelPreconditioner(A)`` with a ``TangentOperator``; csrc/jit/multilevel_free.hip for the
+translations, csrc/jit/multilevel_free_rigid.hip for the rigid-body modes, below).  The hierarchy is that of ``matrix.block_pattern(dofmap, n_nodes)``: every table is the one of a ``TangentMatrix`` of the same
 force (a node of no cell, which that matrix would refuse, has a row of its own block).  Nothing reads fine values: the first argument of ``setup``, ``apply`` and the solve is the tangent of the quadrature points.
 *Level-1 values*, coarse block ``(I, J)``, entry ``(r, s)``: ``f`` = the number of constrained dofs ``D i + r`` among the members ``i`` of
 ``I``, as a double, if ``I == J`` and ``r == s``, else ``0.0``; over the contributions ``(c, a, b)`` with ``agg[dofmap[c][a]] == I`` and
@@ -77,7 +77,23 @@ the status: behind the end of a solve such a product still writes the preconditi
 Restriction, prolongation (skipped at the operator's constrained dofs), smoothing, the closing kernel and the levels ``l >= 2`` are
 the kernels above, unchanged.
 
-LDS of a block: ``lds_bytes(kernel)``.
+*The rigid-body coarse space on an operator* (``MultilevelPreconditioner(A, coarse_space="rigid_body", coordinates=X)``).  Positions,
+offsets, ``P_i = [I_D  B(o_i)]``, the ``(D, Dc)`` transfer kernels of level 0, the ``(Dc, Dc)`` Galerkin kernel of the levels ``l >= 2``,
+the inverses and the cycles are those of the rigid-body coarse space above; level 0 is the operator's as in the last paragraph (its
+own blocks, its products); the contribution lists, their chunks and the element matrices are those of the translations.  Only the
+first Galerkin step is new.  *Level-1 values*, coarse block ``(I, J)``, entry ``(r, s)``, ``0 <= r, s < Dc``: ``f = 0.0``; with a mask and
+``I == J``, over the members ``i`` of ``I``, ascending: ``t = 0.0``; for ``a = 0 .. D - 1`` ascending, where dof ``D i + a`` is constrained:
+``t = t + P_i[a][r] * P_i[a][s]``; then ``f = f + t`` (every member takes part, one with no constrained dof adds ``0.0``; without a mask
+the loop is skipped: the same bits).  Then over the contributions ``(c, a, b)`` of the block, ascending in ``c A A + a A + b``, with ``i =
+dofmap[c][a]`` and ``j = dofmap[c][b]``: ``t = 0.0``; for ``a' = 0 .. D - 1`` ascending, skipped where dof ``D i + a'`` is constrained: ``u =
+0.0``; for ``b' = 0 .. D - 1`` ascending, skipped where dof ``D j + b'`` is constrained: ``u = u + ke[c][a][a'][b][b'] * P_j[b'][s]``; ``t = t +
+P_i[a'][r] * u``; then ``f = f + t``.  A later chunk of cells goes on from the value that is there, so the bits do not depend on
+``A.scratch_bytes``.  This is ``P^T (M K M + I - M) P``, the rigid-body Galerkin step of the assembled route in another order of
+summation: equal to it within rounding, not on the bits; a constrained dof adds its translation's ``1.0`` and its couplings to the
+rotations.  The level-0 offsets go to the device, no level-0 fold list does.  Coordinates that put all nodes of a mesh of more than
+one node at one point are refused on an operator whatever the number of levels (every offset is zero, the rotations vanish).
+
+LDS of a block: ``lds_bytes(kernel)`` (``lds_bytes(FREE_RIGID_GALERKIN_KERNEL, gdim)`` for the gather above).
 """
 
 from __future__ import annotations
@@ -104,6 +120,7 @@ RIGID_RESTRICT_KERNEL = "fcamd_mr_restrict_kernel"
 RIGID_PROLONG_KERNEL = "fcamd_mr_prolong_kernel"
 RIGID_KERNELS = (RIGID_GALERKIN_KERNEL, RIGID_RESTRICT_KERNEL, RIGID_PROLONG_KERNEL)
 FREE_GALERKIN_KERNEL = "fcamd_mf_galerkin_kernel"
+FREE_RIGID_GALERKIN_KERNEL = "fcamd_mfr_galerkin_kernel"
 CYCLES = ("multiplicative", "additive")
 COARSE_SPACES = ("translations", "rigid_body")
 _MODE_QUIET = 3
@@ -111,15 +128,19 @@ _MODE_QUIET = 3
 #: gradients, two in BiCGStab (p -> y, s -> z), and the standalone ``apply`` beside them
 PLANS = 4
 
-__all__ = ["MultilevelPreconditioner", "aggregate", "coarse_dofs", "coarsen", "compile_free_kernels", "compile_kernels", "compile_rigid_kernels",
-           "free_program", "hierarchy", "lds_bytes", "place", "program", "rigid_program"]
+__all__ = ["MultilevelPreconditioner", "aggregate", "coarse_dofs", "coarsen", "compile_free_kernels", "compile_free_rigid_kernels", "compile_kernels",
+           "compile_rigid_kernels", "free_program", "free_rigid_program", "hierarchy", "lds_bytes", "place", "program", "rigid_program"]
 
 
-def lds_bytes(kernel: str = CLOSE_KERNEL) -> int:
+def lds_bytes(kernel: str = CLOSE_KERNEL, gdim: int = 3) -> int:
     """LDS of one block of ``kernel``: the tree of the dot and the last-block flag in the closing kernel, nothing in the other four
-    nor in the three of the rigid-body coarse space; the solver's kernels of the same program: ``solver.lds_bytes(kernel, False)``"""
+    nor in the three of the rigid-body coarse space; the solver's kernels of the same program: ``solver.lds_bytes(kernel, False)``.
+    The first Galerkin step of an operator with the rigid-body space, in ``gdim`` dimensions: per lane a double of an element
+    matrix, a double of an offset and the int of a constrained byte, and four ints per group of 64 (3-D) or 16 (2-D) lanes"""
     if kernel in solver.KERNELS:
         return solver.lds_bytes(kernel, False)
+    if kernel == FREE_RIGID_GALERKIN_KERNEL:
+        return 256 * (8 + 8 + 4) + 256 // {2: 16, 3: 64}[int(gdim)] * 4 * 4
     if kernel in RIGID_KERNELS or kernel == FREE_GALERKIN_KERNEL:
         return 0
     return {CLOSE_KERNEL: 8 * (256 + 2), GALERKIN_KERNEL: 0, RESTRICT_KERNEL: 0, PROLONG_KERNEL: 0, SMOOTH_KERNEL: 0}[kernel]
@@ -188,6 +209,26 @@ def compile_free_kernels(gdim: int, nodes_per_cell: int):
     scratch = kernel_resources(code.log, FREE_GALERKIN_KERNEL)["scratch_bytes"]
     if scratch:
         raise ValueError(f"{name}: {FREE_GALERKIN_KERNEL} compiles with {scratch} bytes of scratch per lane")
+    return code
+
+
+def free_rigid_program(gdim: int, nodes_per_cell: int) -> str:
+    """the program text of the first Galerkin step of a ``TangentOperator`` with the rigid-body coarse space"""
+    return "\n".join([f"#define FCAMD_MF_D {int(gdim)}", f"#define FCAMD_MF_A {int(nodes_per_cell)}", '#include "multilevel_free_rigid.hip"']) + "\n"
+
+
+def compile_free_rigid_kernels(gdim: int, nodes_per_cell: int):
+    """The code object of the first Galerkin step of a ``TangentOperator`` of one cell shape with the rigid-body coarse space (no GPU
+    needed).  Scratch is a ``ValueError``."""
+    if gdim not in (2, 3):
+        raise ValueError(f"the rigid-body coarse space is for 2 or 3 dofs per node, got {gdim}")
+    if nodes_per_cell < 1:
+        raise ValueError("a cell needs at least one node")
+    name = f"multilevel_free_rigid_{gdim}d_{nodes_per_cell}n"
+    code = jit.compile_program(free_rigid_program(gdim, nodes_per_cell), name, FREE_RIGID_GALERKIN_KERNEL)
+    scratch = kernel_resources(code.log, FREE_RIGID_GALERKIN_KERNEL)["scratch_bytes"]
+    if scratch:
+        raise ValueError(f"{name}: {FREE_RIGID_GALERKIN_KERNEL} compiles with {scratch} bytes of scratch per lane")
     return code
 
 
@@ -315,6 +356,15 @@ class FreeArgs(C.Structure):
                 ("first", C.c_int32), ("pad", C.c_int32)]
 
 
+class FreeRigidArgs(C.Structure):
+    """ctypes mirror of fcamd_mfr::Args (multilevel_free_rigid.hip)"""
+
+    _fields_ = [(name, C.c_void_p) for name in ("ke", "blk_ptr", "contrib", "dofmap", "mask", "block_row", "block_col", "mem_ptr", "members", "offsets",
+                                                "values")] + \
+               [("block0", C.c_int64), ("block1", C.c_int64), ("key_lo", C.c_int64), ("key_hi", C.c_int64), ("cell0", C.c_int64),
+                ("first", C.c_int32), ("pad", C.c_int32)]
+
+
 # ---- the seam of level 0 -----------------------------------------------------------------------------------------------------------
 # What the preconditioner asks of its fine level, and nothing else reads ``K``: the pattern the hierarchy is built from, the check of
 # the first argument of a call, the array the inverse kernel reads the nodes' own blocks from, the launches of a product, the first
@@ -377,12 +427,12 @@ class _FreeFine:
         n = self.K.n_cells
         return [(c, min(c + self.chunk_cells, n)) for c in range(0, n, self.chunk_cells)]
 
-    def build(self, levels: list) -> None:
-        """the programs and, with a coarse level, its contribution lists (host)"""
+    def build(self, levels: list, rigid: bool = False) -> None:
+        """the programs and, with a coarse level, its contribution lists (host); ``rigid``: the gather of multilevel_free_rigid.hip"""
         A = self.K
         d_, a_ = A.gdim, A.nodes_per_cell
         self.element_code = _matrix.compile_kernels(d_, a_, A.points_per_cell, A.op.affine)  # (no kernel of it has scratch, or this raises)
-        self.gather_code = compile_free_kernels(d_, a_)
+        self.gather_code = compile_free_rigid_kernels(d_, a_) if rigid else compile_free_kernels(d_, a_)
         if len(levels) < 2:
             return
         fine, coarse = levels[0], levels[1]
@@ -414,7 +464,8 @@ class _FreeFine:
         return tuple(t.data_ptr() for t in held)
 
     def galerkin(self, pc, dev: int, tangent, cap: int) -> None:
-        """the values of level 1 from the tangent: per chunk the element kernel, then the gather of multilevel_free.hip"""
+        """the values of level 1 from the tangent: per chunk the element kernel, then the gather of multilevel_free.hip or, with the
+        rigid-body coarse space, of multilevel_free_rigid.hip"""
         import torch
 
         A, on = self.K, pc._device(dev)
@@ -425,11 +476,24 @@ class _FreeFine:
         weights = A.force._tables(dev)[0]
         mask = A._mask_table(dev)
         t0, t1 = on.tables[0], on.tables[1]
-        n_entries = dd * pc._levels[1].nnzb
-        ga = FreeArgs(on.ke.data_ptr(), t1["blk_ptr"].data_ptr(), t1["contrib"].data_ptr(), dofmap.data_ptr(), 0 if mask is None else mask.data_ptr(),
-                      t1["block_row"].data_ptr(), t1["indices"].data_ptr(), t0["mem_ptr"].data_ptr(), t0["members"].data_ptr(), on.values[1].data_ptr(),
-                      0, n_entries, 0, 0, 0, 1, 0)
-        gather_blocks = pc._blocks(n_entries, cap)  # a lane per entry
+        common = (on.ke.data_ptr(), t1["blk_ptr"].data_ptr(), t1["contrib"].data_ptr(), dofmap.data_ptr(), 0 if mask is None else mask.data_ptr(),
+                  t1["block_row"].data_ptr(), t1["indices"].data_ptr(), t0["mem_ptr"].data_ptr(), t0["members"].data_ptr())
+        if pc._rigid:  # multilevel_free_rigid.hip: a group of lanes per coarse block
+            lanes, what = {2: 16, 3: 64}[d_], "MultilevelPreconditioner first rigid-body Galerkin launch"
+            ga = FreeRigidArgs(*common, t0["offset"].data_ptr(), on.values[1].data_ptr(), 0, 0, 0, 0, 0, 1, 0)
+        else:  # multilevel_free.hip: a lane per entry
+            lanes, what = dd, "MultilevelPreconditioner first Galerkin launch"
+            ga = FreeArgs(*common, on.values[1].data_ptr(), 0, 0, 0, 0, 0, 1, 0)
+
+        def cover(lo, hi):
+            """the launch covers the coarse blocks ``lo .. hi``: its thread blocks"""
+            if pc._rigid:
+                ga.block0, ga.block1 = lo, hi
+            else:
+                ga.entry0, ga.n_entries = dd * lo, dd * hi
+            return pc._blocks(lanes * (hi - lo), cap)
+
+        gather_blocks = cover(0, pc._levels[1].nnzb)
         jstride = 8 * dd * (1 if A.op.affine else q_)
         with torch.cuda.device(dev):
             for k, (c0, c1) in enumerate(self.chunks()):
@@ -439,9 +503,8 @@ class _FreeFine:
                 jit.launch(self.element_code, dev, min((tiles + 3) // 4, cap), ea, "MultilevelPreconditioner element launch")  # a wave per tile, 4 waves per block
                 ga.key_lo, ga.key_hi, ga.cell0, ga.first = c0 * a_ * a_, c1 * a_ * a_, c0, 1 if k == 0 else 0
                 if k:  # the first chunk starts every entry; a later one visits the coarse blocks its cells touch
-                    ga.entry0, ga.n_entries = dd * self.chunk_blocks[k][0], dd * self.chunk_blocks[k][1]
-                    gather_blocks = pc._blocks(ga.n_entries - ga.entry0, cap)
-                jit.launch(self.gather_code, dev, gather_blocks, ga, "MultilevelPreconditioner first Galerkin launch")
+                    gather_blocks = cover(*self.chunk_blocks[k])
+                jit.launch(self.gather_code, dev, gather_blocks, ga, what)
 
 
 class _OnDevice:
@@ -471,11 +534,15 @@ class _OnDevice:
             if lv.agg is not None:
                 # (an operator's level 0 has no blocks to fold: its fold lists, as long as the fine pattern, stay on the host)
                 folds = () if l == 0 and pc._seam.free else ("fold_ptr", "fold")
-                for name in ("agg", "mem_ptr", "members") + folds + (("block_row", "indices", "offset") if pc._rigid else ()):
+                # (the rigid-body transfers read the offsets; the (Df, Dc) Galerkin kernel of a level with values the nodes of its blocks too)
+                rigid = () if not pc._rigid else ("offset",) if l == 0 and pc._seam.free else ("block_row", "indices", "offset")
+                for name in ("agg", "mem_ptr", "members") + folds + rigid:
                     if name not in t:  # (a coarse level's column nodes are there already)
                         t[name] = to_device(getattr(lv, name), d)
             if l == 1 and pc._seam.free:  # the lists of the first Galerkin step
-                t["blk_ptr"], t["contrib"], t["block_row"] = (to_device(x, d) for x in (pc._seam.blk_ptr, pc._seam.contributions, pc._seam.block_row))
+                t["blk_ptr"], t["contrib"] = (to_device(x, d) for x in (pc._seam.blk_ptr, pc._seam.contributions))
+                if "block_row" not in t:  # (with the rigid-body space and a level 2 it is there already)
+                    t["block_row"] = to_device(pc._seam.block_row, d)
             self.tables.append(t)
             self.inv.append(zeros(dofs[l]**2 * lv.n_nodes))
             self.q.append(zeros(dofs[l] * lv.n_nodes))
@@ -513,7 +580,9 @@ class MultilevelPreconditioner:
     ``TangentMatrix`` of the same force, ``setup(tangent)``, ``apply(tangent, r, out=None)`` and ``ConjugateGradient(A, preconditioner=pc)(tangent,
     b)`` take the ``S*S n_points`` tangent where the values stood, and no matrix is formed: level 1 is gathered from the element matrices,
     which pass through a scratch of ``A.scratch_bytes`` (less than one tile of ``matrix.cells_per_tile`` element matrices: a
-    ``ValueError``).  Translations only: ``coarse_space="rigid_body"`` on an operator is a ``ValueError``.  A node in no cell has a zero
+    ``ValueError``).  ``coarse_space="rigid_body"`` with ``coordinates`` works on an operator as on a matrix (level 1 is gathered as
+    ``P_i^T ke P_j`` with the offsets of level 0); there, coordinates that put all nodes at one point are a ``ValueError`` whatever the
+    number of levels: the rotations vanish.  A node in no cell has a zero
     block of its own on every level it reaches: ``setup`` and ``apply`` end with the status ``singular_block`` (nothing is applied), and
     ``ConjugateGradient`` refuses such an operator at construction."""
 
@@ -525,9 +594,6 @@ class MultilevelPreconditioner:
             raise ValueError(f"cycle must be one of {CYCLES}, got {cycle!r}")
         if not (isinstance(coarse_space, str) and coarse_space in COARSE_SPACES):
             raise ValueError(f"coarse_space must be one of {COARSE_SPACES}, got {coarse_space!r}")
-        if isinstance(K, TangentOperator) and coarse_space != "translations":
-            raise ValueError(f"coarse_space={coarse_space!r} needs the matrix: on a TangentOperator the first Galerkin step is the sum of the element matrices, "
-                             'which is P^T K P for the translations only (with rotations it is P_i^T ke P_j with the offsets); use coarse_space="translations"')
         if coarse_space == "translations":
             if coordinates is not None:
                 raise ValueError('coordinates belong to coarse_space="rigid_body"; the translations need none')
@@ -542,6 +608,9 @@ class MultilevelPreconditioner:
                 raise ValueError(f"coordinates must have the shape {(K.n_nodes, K.gdim)}, got {coordinates.shape}")
             if not np.isfinite(coordinates).all():
                 raise ValueError("coordinates must be finite")
+            if isinstance(K, TangentOperator) and K.gdim > 1 and K.n_nodes > 1 and (coordinates == coordinates[0]).all():
+                raise ValueError(f'coordinates put all {K.n_nodes} nodes at one point: every offset is zero and the rotations vanish, so coarse_space="rigid_body" '
+                                 'has a singular coarse level; pass the positions of the nodes or use coarse_space="translations"')
         if isinstance(omega, bool) or not isinstance(omega, (int, float, np.integer, np.floating)):
             raise TypeError(f"omega must be a number, got {type(omega).__name__}")
         if not (omega > 0.0 and np.isfinite(omega)):
@@ -579,7 +648,7 @@ class MultilevelPreconditioner:
         else:
             self._code = self._coarse_code = compile_kernels(K.gdim)
         if seam.free:
-            seam.build(self._levels)
+            seam.build(self._levels, self._rigid)
         self._on = {}  # device index -> _OnDevice
 
     # ---- what was asked for (read-only) ----------------------------------------------------------------------------------------
@@ -653,8 +722,11 @@ class MultilevelPreconditioner:
         if self._rigid:  # the three transfer kernels of the pair (D, Dc), and under "coarse" every kernel of the coarse program by its name
             r.update({"rigid_" + kernel[len("fcamd_mr_"): -len("_kernel")]: kernel_resources(self._code.log, kernel) for kernel in RIGID_KERNELS})
             r["coarse"] = {kernel: kernel_resources(self._coarse_code.log, kernel) for kernel in solver.KERNELS + KERNELS + RIGID_KERNELS}
-        if self._seam.free:  # the two kernels of the first Galerkin step of an operator
-            r["free_galerkin"] = kernel_resources(self._seam.gather_code.log, FREE_GALERKIN_KERNEL)
+        if self._seam.free:  # the two kernels of the first Galerkin step of an operator: its gather (of either coarse space) and the element kernel
+            if self._rigid:
+                r["free_rigid_galerkin"] = kernel_resources(self._seam.gather_code.log, FREE_RIGID_GALERKIN_KERNEL)
+            else:
+                r["free_galerkin"] = kernel_resources(self._seam.gather_code.log, FREE_GALERKIN_KERNEL)
             r["free_element"] = kernel_resources(self._seam.element_code.log, _matrix.ELEMENT_KERNEL)
         return r
 
@@ -668,8 +740,8 @@ class MultilevelPreconditioner:
         return self._coarse_code.log
 
     @staticmethod
-    def lds_bytes(kernel: str = CLOSE_KERNEL) -> int:
-        return lds_bytes(kernel)
+    def lds_bytes(kernel: str = CLOSE_KERNEL, gdim: int = 3) -> int:
+        return lds_bytes(kernel, gdim)
 
     @property
     def device(self) -> int:
