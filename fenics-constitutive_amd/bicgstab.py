@@ -2,8 +2,8 @@
 
 ``BiCGStab(K)`` solves ``K x = b`` for the values array a ``TangentMatrix`` wrote ("bsr" or "csr") when ``K`` is not symmetric --
 Drucker-Prager with ``b != b_flow``, a ``JaumannRate`` around any law, a ``UserLaw`` with a non-associated tangent --, where
-``ConjugateGradient`` ends as ``indefinite`` or ``maxiter`` or drifts.  Arguments, validation, errors, ``SolveResult`` and the
-preconditioners are ``ConjugateGradient``'s (``solver.py``); one status is new, ``"breakdown"``.
+``ConjugateGradient`` ends as ``indefinite`` or ``maxiter`` or drifts.  Arguments, validation, errors, looks and ``SolveResult`` are
+those of the driver both solvers stand on (``solver._Krylov``); one status is new, ``"breakdown"``.
 
 Five run-time compiled kernels (``csrc/jit/bicgstab.hip``) beside the matrix-vector, inverse and dot kernels of
 ``csrc/jit/conjugate_gradient.hip``, which the program includes.  The arithmetic is fixed as in ``solver.py`` -- the same
@@ -44,8 +44,9 @@ launch, no grid-wide barrier, no kernel that waits on a flag.
 
 LDS of a block: ``lds_bytes(kernel, preconditioner)``.
 
-``BiCGStab`` takes a ``TangentMatrix`` only.  The same recurrence on a matrix-free ``TangentOperator`` -- this module's start, half-step,
-full-step and direction kernels around the operator's own product -- is ``bicgstab_free.MatrixFreeBiCGStab``.
+The recurrence's host side is ``_BiCGStab``, written once on the operator seam of ``solver.py``.  ``BiCGStab`` takes a
+``TangentMatrix`` only and adds the assembled products (``K x0`` by the conjugate gradients' matrix-vector kernel, the product kernel
+above); ``bicgstab_free.MatrixFreeBiCGStab`` takes a ``TangentOperator`` and adds the operator's own.
 """
 
 from __future__ import annotations
@@ -55,10 +56,10 @@ import ctypes as C
 import numpy as np
 
 from . import jit, solver
-from .force import kernel_resources
+from .force import compile_without_scratch, kernel_resources
 from .gradient import BLOCKS_PER_CU, LDS_CAP
 from .matrix import TangentMatrix
-from .solver import SEG, SLAB, SolveResult
+from .solver import SEG, SLAB
 
 PRODUCT_KERNEL = "fcamd_bcg_product_kernel"
 START_KERNEL = "fcamd_bcg_start_kernel"
@@ -118,12 +119,7 @@ def compile_kernels(gdim: int, preconditioner="block_jacobi", slab: int = SLAB):
         raise ValueError(f"the slab must be a positive multiple of 128 doubles, got {slab}")
     if lds_bytes(PRODUCT_KERNEL, slab=slab) > LDS_CAP:
         raise ValueError(f"four wave regions of {slab} doubles need {lds_bytes(PRODUCT_KERNEL, slab=slab)} bytes of LDS per block; at most {LDS_CAP} fit")
-    code = jit.compile_program(program(gdim, kind, slab), f"bicgstab_{gdim}d", PRODUCT_KERNEL)
-    for kernel in KERNELS + SHARED_KERNELS:
-        scratch = kernel_resources(code.log, kernel)["scratch_bytes"]
-        if scratch:
-            raise ValueError(f"bicgstab_{gdim}d: {kernel} compiles with {scratch} bytes of scratch per lane")
-    return code
+    return compile_without_scratch(program(gdim, kind, slab), f"bicgstab_{gdim}d", PRODUCT_KERNEL, KERNELS + SHARED_KERNELS)
 
 
 class Params(C.Structure):
@@ -137,16 +133,72 @@ class _Control(solver._Control):
     atol and maxiter lie where they do there)"""
 
     def __init__(self, dev: int, nseg: int):
-        import torch
-
-        super().__init__(dev, nseg)
-        self.device_block = torch.zeros(_SCALARS, dtype=torch.float64, device=torch.device("cuda", dev))
-        self.pinned = torch.zeros(_SCALARS, dtype=torch.float64).pin_memory()
-        self.host = self.pinned.numpy()
-        self.ints = self.host.view(np.int32)
+        super().__init__(dev, nseg, _SCALARS)
 
 
-class BiCGStab:
+class _BiCGStab(solver._Krylov):
+    """The recurrence of the module docstring on the driver of ``solver.py``, written once for both operators: the workspace, the
+    start and one iteration -- cycle, product, half step, cycle, product, full step, direction.  A subclass accepts its kind of
+    ``K`` and supplies ``_first_product(dev, values, a, x, v)``, which enqueues ``v = K x0``, and ``_products(dev, values, a, control)``, the
+    function ``product(vector, result, other, dots)`` that enqueues ``result = K vector`` with the dots ``dots`` against ``other``."""
+
+    _STATUSES = STATUSES
+
+    def __init__(self, K, preconditioner, rtol, atol, maxiter, check_every):
+        super().__init__(K, preconditioner, rtol, atol, maxiter, check_every)
+        self._kind = 2 if self._ml is not None else _kind(self.preconditioner)
+        self._code = compile_kernels(K.gdim, self._kind)
+
+    def _workspace(self, dev: int):
+        """(control, r, rhat, p, v, t, y, z, inv)"""
+        w = self._work.get(dev)
+        if w is None:
+            import torch
+
+            d = torch.device("cuda", dev)
+
+            def vector():
+                return torch.zeros(self.n, dtype=torch.float64, device=d)
+
+            r, rhat, p, v, t = (vector() for _ in range(5))
+            y, z = (vector(), vector()) if self._kind else (p, r)  # without a preconditioner y is p and z is s, which lies over r
+            inv = torch.zeros(self.K.gdim**2 * self.K.n_nodes if self._kind == 1 else 2, dtype=torch.float64, device=d)
+            w = self._work[dev] = (_Control(dev, self._op.nseg), r, rhat, p, v, t, y, z, inv)
+        return w
+
+    def _start(self, dev: int, values, b, x, has_x0: bool, work):
+        control, r, rhat, p, v, t, y, z, inv = work
+        code, ml, n, name = self._code, self._ml, self.n, self._name
+        a = Params()
+        a.cg = self._op.args(dev, values, control)
+        a.cg.b, a.cg.x, a.cg.r, a.cg.z, a.cg.p, a.cg.inv = (w.data_ptr() for w in (b, x, r, z, p, inv))
+        a.rhat, a.v, a.t, a.y = (w.data_ptr() for w in (rhat, v, t, y))
+        a.cg.has_x0 = 1 if has_x0 else 0
+        cap, blocks = BLOCKS_PER_CU * jit.num_cu(dev), self._op.blocks(dev)
+        self._inverses(dev, values, a.cg, control)
+        a.cg.q = v.data_ptr()
+        if has_x0:
+            self._first_product(dev, values, a, x, v)
+        jit.launch(code, dev, blocks, a, f"{name} start launch", kernel=START_KERNEL)
+        direction_blocks = max(1, min(-(-n // _CHUNK) if self._kind == 1 else -(-(n // 2) // 256), cap))
+        product = self._products(dev, values, a, control)
+        half, full, direction = f"{name} half-step launch", f"{name} full-step launch", f"{name} direction launch"
+
+        def iterate():
+            if ml is not None:
+                ml._cycle(dev, values, control, p.data_ptr(), y.data_ptr())
+            product(y, v, rhat, _DOT_V)
+            jit.launch(code, dev, blocks, a, half, kernel=HALF_KERNEL)
+            if ml is not None:
+                ml._cycle(dev, values, control, r.data_ptr(), z.data_ptr())
+            product(z, t, r, _DOT_T)
+            jit.launch(code, dev, blocks, a, full, kernel=FULL_KERNEL)
+            jit.launch(code, dev, direction_blocks, a, direction, kernel=DIRECTION_KERNEL)
+
+        return iterate
+
+
+class BiCGStab(_BiCGStab):
     """``solver(values, b, x0=None, out=None) -> SolveResult``: ``K x = b`` by right-preconditioned BiCGStab on the GPU, for a ``K``
     that need not be symmetric.
 
@@ -166,45 +218,8 @@ class BiCGStab:
                  check_every: int = 16):
         if not isinstance(K, TangentMatrix):
             raise TypeError(f"K must be a TangentMatrix, got {type(K).__name__}")
-        from .multilevel import MultilevelPreconditioner
+        super().__init__(K, preconditioner, rtol, atol, maxiter, check_every)
 
-        if isinstance(preconditioner, str) and preconditioner == "multilevel":
-            pass  # built below, once everything else has been validated
-        elif isinstance(preconditioner, MultilevelPreconditioner):
-            if preconditioner.K is not K:
-                raise ValueError("the MultilevelPreconditioner was built for another matrix")
-        elif not (preconditioner is None or (isinstance(preconditioner, str) and preconditioner == "block_jacobi")):
-            raise ValueError(f"preconditioner must be one of {solver.PRECONDITIONERS + ('multilevel',)} or a MultilevelPreconditioner of K, got {preconditioner!r}")
-        for name, v in (("rtol", rtol), ("atol", atol)):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-                raise TypeError(f"{name} must be a number, got {type(v).__name__}")
-            if not (v >= 0.0 and np.isfinite(v)):
-                raise ValueError(f"{name} must be finite and not negative, got {v}")
-        n = K.shape[0]
-        if maxiter is None:
-            maxiter = 10 * n
-        for name, v, least in (("maxiter", maxiter, 0), ("check_every", check_every, 1)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise TypeError(f"{name} must be an integer, got {type(v).__name__}")
-            if v < least or v >= 2**31:
-                raise ValueError(f"{name} must lie in [{least}, 2^31), got {v}")
-        missing = np.flatnonzero(K.diag_block < 0)
-        if missing.size:
-            raise ValueError(f"node {int(missing[0])} has no diagonal block in the pattern: its row is empty, the matrix singular")
-        if isinstance(preconditioner, str) and preconditioner == "multilevel":
-            preconditioner = MultilevelPreconditioner(K)
-        self.K = K
-        self.preconditioner = preconditioner
-        self.rtol, self.atol, self.maxiter, self.check_every = float(rtol), float(atol), int(maxiter), int(check_every)
-        self._op = solver._operator(K)
-        #: the multilevel preconditioner (its cycle runs from its own program on this solver's control block), or None
-        self._ml = preconditioner if isinstance(preconditioner, MultilevelPreconditioner) else None
-        self._kind = 2 if self._ml is not None else _kind(preconditioner)
-        self._code = compile_kernels(K.gdim, self._kind)
-        self.n = n
-        self._work = {}  # device index -> (control, r, rhat, p, v, t, y, z, inv)
-
-    # ---- what the compiler made ------------------------------------------------------------------------------------------------
     @property
     def resources(self) -> dict:
         """``{"vgprs", "sgprs", "scratch_bytes", "lds_bytes", "waves_per_simd", ...}`` of the product kernel, under "start", "half",
@@ -216,100 +231,19 @@ class BiCGStab:
         r["slab"] = SLAB
         return r
 
-    @property
-    def compile_log(self) -> str:
-        return self._code.log
-
-    @property
-    def device(self) -> int:
-        return self.K.device
-
     def lds_bytes(self, kernel: str = PRODUCT_KERNEL) -> int:
         return lds_bytes(kernel, self._kind)
 
-    def _workspace(self, dev: int):
-        w = self._work.get(dev)
-        if w is None:
-            import torch
+    def _first_product(self, dev: int, values, a: Params, x, v) -> None:
+        """``K x0`` into ``v`` (``a.cg.q``), by the conjugate gradients' product"""
+        a.cg.va, a.cg.mode = x.data_ptr(), solver._MODE_PLAIN
+        jit.launch(self._code, dev, self._op.blocks(dev), a.cg, "BiCGStab matrix-vector launch", kernel=solver.MATVEC_KERNEL)
 
-            d = torch.device("cuda", dev)
+    def _products(self, dev: int, values, a: Params, control):
+        code, blocks = self._code, self._op.blocks(dev)
 
-            def vector():
-                return torch.zeros(self.n, dtype=torch.float64, device=d)
+        def product(vector, result, other, dots):
+            a.cg.va, a.cg.q, a.cg.vb, a.cg.mode = vector.data_ptr(), result.data_ptr(), other.data_ptr(), dots
+            jit.launch(code, dev, blocks, a, "BiCGStab product launch", kernel=PRODUCT_KERNEL)
 
-            r, rhat, p, v, t = (vector() for _ in range(5))
-            y, z = (vector(), vector()) if self._kind else (p, r)  # without a preconditioner y is p and z is s, which lies over r
-            inv = torch.zeros(self.K.gdim**2 * self.K.n_nodes if self._kind == 1 else 2, dtype=torch.float64, device=d)
-            w = self._work[dev] = (_Control(dev, self._op.nseg), r, rhat, p, v, t, y, z, inv)
-        return w
-
-    def __call__(self, values, b, x0=None, out=None) -> SolveResult:
-        """solve ``K x = b`` (synchronous at its end)"""
-        import torch
-
-        K, dev, n = self.K, self.device, self.n
-        K._check("values", values, K.nnz, dev)
-        K._check("b", b, n, dev)
-        if x0 is not None:
-            K._check("x0", x0, n, dev)
-        if out is not None:
-            K._check("out", out, n, dev)
-            if solver._overlap(out, b):
-                raise ValueError("out must not alias b")
-            if x0 is not None and solver._overlap(out, x0) and out.data_ptr() != x0.data_ptr():
-                raise ValueError("out may be x0 itself, not a part of it")
-        op = self._op
-        with torch.cuda.device(dev):
-            d = torch.device("cuda", dev)
-            if out is None:
-                x = torch.zeros(n, dtype=torch.float64, device=d) if x0 is None else x0.clone()
-            else:
-                x = out
-                if x0 is None:
-                    x.zero_()
-                elif x.data_ptr() != x0.data_ptr():
-                    x.copy_(x0)
-            if n == 0:
-                return SolveResult(x, 0, True, "converged", 0.0, 0.0, 0)
-            control, r, rhat, p, v, t, y, z, inv = self._workspace(dev)
-            control.upload(self.rtol, self.atol, self.maxiter)
-            a = Params()
-            a.cg = op.args(dev, values, control)
-            a.cg.b, a.cg.x, a.cg.r, a.cg.z, a.cg.p, a.cg.inv = (w.data_ptr() for w in (b, x, r, z, p, inv))
-            a.rhat, a.v, a.t, a.y = (w.data_ptr() for w in (rhat, v, t, y))
-            a.cg.has_x0 = 0 if x0 is None else 1
-            code, cap, blocks = self._code, BLOCKS_PER_CU * jit.num_cu(dev), op.blocks(dev)
-            ml = self._ml
-            if ml is not None:
-                ml._setup(dev, values, control)
-            elif self._kind == 1:
-                jit.launch(code, dev, max(1, min(-(-K.n_nodes // 256), cap)), a.cg, "BiCGStab inverse launch", kernel=solver.INVERSE_KERNEL)
-            a.cg.q = v.data_ptr()
-            if x0 is not None:  # K x0 into v, by the conjugate gradients' product
-                a.cg.va, a.cg.mode = x.data_ptr(), solver._MODE_PLAIN
-                jit.launch(code, dev, blocks, a.cg, "BiCGStab matrix-vector launch", kernel=solver.MATVEC_KERNEL)
-            jit.launch(code, dev, blocks, a, "BiCGStab start launch", kernel=START_KERNEL)
-            direction_blocks = max(1, min(-(-n // _CHUNK) if self._kind == 1 else -(-(n // 2) // 256), cap))
-
-            def product(vector, result, other, dots):
-                a.cg.va, a.cg.q, a.cg.vb, a.cg.mode = vector.data_ptr(), result.data_ptr(), other.data_ptr(), dots
-                jit.launch(code, dev, blocks, a, "BiCGStab product launch", kernel=PRODUCT_KERNEL)
-
-            control.download(dev)  # a solve that ends at its start (b = 0, a singular block, maxiter = 0) enqueues no iteration
-            looks = 1
-            while int(control.ints[solver._STATUS]) == 0:
-                for _ in range(self.check_every):
-                    if ml is not None:
-                        ml._cycle(dev, values, control, p.data_ptr(), y.data_ptr())
-                    product(y, v, rhat, _DOT_V)
-                    jit.launch(code, dev, blocks, a, "BiCGStab half-step launch", kernel=HALF_KERNEL)
-                    if ml is not None:
-                        ml._cycle(dev, values, control, r.data_ptr(), z.data_ptr())
-                    product(z, t, r, _DOT_T)
-                    jit.launch(code, dev, blocks, a, "BiCGStab full-step launch", kernel=FULL_KERNEL)
-                    jit.launch(code, dev, direction_blocks, a, "BiCGStab direction launch", kernel=DIRECTION_KERNEL)
-                control.download(dev)
-                looks += 1
-            h, status = control.host, int(control.ints[solver._STATUS])
-            return SolveResult(x, int(control.ints[solver._ITERATIONS]), status == 1, STATUSES[status], float(np.sqrt(h[solver._RR])),
-                               float(np.sqrt(h[solver._BB])), looks)
+        return product

@@ -18,13 +18,11 @@ complete are the partials of ``solver_util.ordered_dot``, and the trees, the sec
 (``rv``; ``ts``, ``tt``, ``omega = ts / tt``; a zero or non-finite ``rv``, ``tt`` or ``omega``: ``breakdown``) are those of that kernel.  The
 second dot adds no pass over memory: ``y`` is in the lane's register.  No floating-point atomics, no MFMA, ``-ffp-contract=off``.
 
-*The solver.*  The recurrence, the statuses, the control block (``bicgstab._Control``, 128 bytes), the looks and ``check_every`` are
-``BiCGStab``'s (``bicgstab.py``, module docstring), and the start, half-step, full-step and direction kernels are those of
-``bicgstab.compile_kernels(A.gdim, kind)``, unchanged; only the product differs -- element launch, then node-dots launch -- and
-``A x0``, which is the operator's quiet product.  Block-Jacobi is formed as ``ConjugateGradient(A)`` forms it
-(``A.diagonal_blocks(tangent)`` into a block array of the solver's, inverted by ``solver.INVERSE_KERNEL`` over the diagonal pattern);
-the multilevel preconditioner is the instance built on the same ``A``, its cycle run before either product.  Per iteration six
-launches -- element, node-dots, half step, element, node-dots, full step -- and the direction kernel, seven, plus the cycles'.
+*The solver.*  ``MatrixFreeBiCGStab`` is ``bicgstab._BiCGStab`` (the recurrence of ``bicgstab.py``'s module docstring, its control block
+and its start, half-step, full-step and direction kernels of ``bicgstab.compile_kernels(A.gdim, kind)``, unchanged) on the driver and
+the operator seam of ``solver.py``, which form block-Jacobi and the multilevel setup as for ``ConjugateGradient(A)``.  This module
+adds only the product -- element launch, then node-dots launch -- and ``A x0``, which is the operator's quiet product.  Per iteration
+six launches -- element, node-dots, half step, element, node-dots, full step -- and the direction kernel, seven, plus the cycles'.
 
 ``product(A, tangent, va, vb, both=False)`` runs the kernel alone.
 """
@@ -33,13 +31,10 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
-
 from . import bicgstab, jit, solver
 from .bicgstab import STATUSES
-from .force import kernel_resources
-from .gradient import BLOCKS_PER_CU
-from .solver import SEG, SolveResult
+from .force import compile_without_scratch, kernel_resources
+from .solver import SEG
 from .tangent_operator import ELEMENT_KERNEL, MODE_ITERATE, MODE_QUIET, NodeArgs, TangentOperator
 
 NODE_DOTS_KERNEL = "fcamd_tangent_operator_node_dots_kernel"
@@ -66,11 +61,7 @@ def compile_kernels(gdim: int, nodes_per_cell: int, points_per_cell: int, affine
     if gdim not in (1, 2, 3):
         raise ValueError(f"the geometric dimension must be 1, 2 or 3, got {gdim}")
     name = f"bicgstab_free_{gdim}d_{nodes_per_cell}n_{points_per_cell}q"
-    code = jit.compile_program(program(gdim, nodes_per_cell, points_per_cell, affine, slab, waves), name, NODE_DOTS_KERNEL)
-    scratch = kernel_resources(code.log, NODE_DOTS_KERNEL)["scratch_bytes"]
-    if scratch:
-        raise ValueError(f"{name}: {NODE_DOTS_KERNEL} compiles with {scratch} bytes of scratch per lane")
-    return code
+    return compile_without_scratch(program(gdim, nodes_per_cell, points_per_cell, affine, slab, waves), name, NODE_DOTS_KERNEL, (NODE_DOTS_KERNEL,))
 
 
 class NodeDotsArgs(C.Structure):
@@ -128,7 +119,7 @@ def product(A: TangentOperator, tangent, va, vb, both: bool = False, out=None):
     if not isinstance(A, TangentOperator):
         raise TypeError(f"A must be a TangentOperator, got {type(A).__name__}")
     dev, n = A.device, A.shape[0]
-    A._check("tangent", tangent, A.tangent_dim * A.n_points, dev)
+    solver._operator(A).check(tangent, dev)
     A._check("va", va, n, dev)
     A._check("vb", vb, n, dev)
     if out is not None:
@@ -149,7 +140,7 @@ def product(A: TangentOperator, tangent, va, vb, both: bool = False, out=None):
     return (out, float(h[_TS]), float(h[_TT])) if both else (out, float(h[_RV]))
 
 
-class MatrixFreeBiCGStab:
+class MatrixFreeBiCGStab(bicgstab._BiCGStab):
     """``solver(tangent, b, x0=None, out=None) -> SolveResult``: ``A x = b`` by right-preconditioned BiCGStab on the GPU, ``A`` a
     ``TangentOperator`` whose tangent need not be symmetric and no matrix anywhere.
 
@@ -168,47 +159,10 @@ class MatrixFreeBiCGStab:
                  check_every: int = 16):
         if not isinstance(A, TangentOperator):
             raise TypeError(f"A must be a TangentOperator, got {type(A).__name__}")
-        from .multilevel import MultilevelPreconditioner
-
-        if isinstance(preconditioner, str) and preconditioner == "multilevel":
-            raise ValueError('preconditioner="multilevel" builds the multilevel preconditioner of a matrix: with a TangentOperator A pass the instance, '
-                             f"MultilevelPreconditioner(A), or one of {solver.PRECONDITIONERS}")
-        if isinstance(preconditioner, MultilevelPreconditioner):
-            if preconditioner.K is not A:
-                raise ValueError("the MultilevelPreconditioner was built for another object: the multilevel preconditioner of a TangentOperator A is "
-                                 "MultilevelPreconditioner(A), built on this very operator")
-        elif not (preconditioner is None or (isinstance(preconditioner, str) and preconditioner == "block_jacobi")):
-            raise ValueError(f"preconditioner must be one of {solver.PRECONDITIONERS} or a MultilevelPreconditioner of A, got {preconditioner!r}")
-        for name, v in (("rtol", rtol), ("atol", atol)):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-                raise TypeError(f"{name} must be a number, got {type(v).__name__}")
-            if not (v >= 0.0 and np.isfinite(v)):
-                raise ValueError(f"{name} must be finite and not negative, got {v}")
-        n = A.shape[0]
-        if maxiter is None:
-            maxiter = 10 * n
-        for name, v, least in (("maxiter", maxiter, 0), ("check_every", check_every, 1)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise TypeError(f"{name} must be an integer, got {type(v).__name__}")
-            if v < least or v >= 2**31:
-                raise ValueError(f"{name} must lie in [{least}, 2^31), got {v}")
-        missing = np.flatnonzero(A.valence == 0)
-        if missing.size:
-            raise ValueError(f"node {int(missing[0])} belongs to no cell: it has no diagonal block, its row is empty, the matrix singular")
-        self.A = self.K = A
-        self.preconditioner = preconditioner
-        self.rtol, self.atol, self.maxiter, self.check_every = float(rtol), float(atol), int(maxiter), int(check_every)
-        self._op = solver._operator(A)
-        #: the multilevel preconditioner (its cycle runs from its own program on this solver's control block), or None
-        self._ml = preconditioner if isinstance(preconditioner, MultilevelPreconditioner) else None
-        self._kind = 2 if self._ml is not None else bicgstab._kind(preconditioner)
-        self._code = bicgstab.compile_kernels(A.gdim, self._kind)
+        super().__init__(A, preconditioner, rtol, atol, maxiter, check_every)
+        self.A = A
         self._product = _product(A)
-        self.n = n
-        self._work = {}  # device index -> (control, r, rhat, p, v, t, y, z, inv)
-        self._work_blocks = {}  # device index -> the block array of block-Jacobi
 
-    # ---- what the compiler made ------------------------------------------------------------------------------------------------
     @property
     def resources(self) -> dict:
         """``{"vgprs", "sgprs", "scratch_bytes", "lds_bytes", "waves_per_simd", ...}`` of the node-dots kernel, the same under
@@ -227,107 +181,20 @@ class MatrixFreeBiCGStab:
         """hiprtc's log of the node-dots program, then that of the program of ``bicgstab.compile_kernels``"""
         return self._product.code.log + self._code.log
 
-    @property
-    def device(self) -> int:
-        return self.A.device
-
     def lds_bytes(self, kernel: str = NODE_DOTS_KERNEL) -> int:
         """LDS of one block of ``kernel``: the tree of the dots and the last-block flag in the node-dots kernel; else as on ``BiCGStab``"""
         if kernel == NODE_DOTS_KERNEL:
             return 8 * (256 + 2)
         return bicgstab.lds_bytes(kernel, self._kind)
 
-    def _workspace(self, dev: int):
-        w = self._work.get(dev)
-        if w is None:
-            import torch
+    def _first_product(self, dev: int, tangent, a, x, v) -> None:
+        """``A x0`` into ``v``, by the operator's quiet product"""
+        self.A._apply(dev, tangent.data_ptr(), x.data_ptr(), v.data_ptr(), MODE_QUIET)
 
-            d = torch.device("cuda", dev)
+    def _products(self, dev: int, tangent, a, control):
+        launch, tangent_ptr = self._product.launch, tangent.data_ptr()
 
-            def vector():
-                return torch.zeros(self.n, dtype=torch.float64, device=d)
+        def product(vector, result, other, dots):
+            launch(dev, tangent_ptr, vector.data_ptr(), result.data_ptr(), other.data_ptr(), dots, control)
 
-            r, rhat, p, v, t = (vector() for _ in range(5))
-            y, z = (vector(), vector()) if self._kind else (p, r)  # without a preconditioner y is p and z is s, which lies over r
-            inv = torch.zeros(self.A.gdim**2 * self.A.n_nodes if self._kind == 1 else 2, dtype=torch.float64, device=d)
-            w = self._work[dev] = (bicgstab._Control(dev, self._op.nseg), r, rhat, p, v, t, y, z, inv)
-        return w
-
-    def _diagonal_blocks(self, dev: int):
-        """the block array of block-Jacobi, ``[n_nodes][D][D]``, one per device"""
-        blocks = self._work_blocks.get(dev)
-        if blocks is None:
-            import torch
-
-            blocks = self._work_blocks[dev] = torch.zeros(self.A.gdim**2 * self.A.n_nodes, dtype=torch.float64, device=torch.device("cuda", dev))
-        return blocks
-
-    def __call__(self, tangent, b, x0=None, out=None) -> SolveResult:
-        """solve ``A x = b`` for this tangent (synchronous at its end)"""
-        import torch
-
-        A, dev, n = self.A, self.device, self.n
-        A._check("tangent", tangent, A.tangent_dim * A.n_points, dev)
-        A._check("b", b, n, dev)
-        if x0 is not None:
-            A._check("x0", x0, n, dev)
-        if out is not None:
-            A._check("out", out, n, dev)
-            if solver._overlap(out, b):
-                raise ValueError("out must not alias b")
-            if x0 is not None and solver._overlap(out, x0) and out.data_ptr() != x0.data_ptr():
-                raise ValueError("out may be x0 itself, not a part of it")
-        op = self._op
-        with torch.cuda.device(dev):
-            d = torch.device("cuda", dev)
-            if out is None:
-                x = torch.zeros(n, dtype=torch.float64, device=d) if x0 is None else x0.clone()
-            else:
-                x = out
-                if x0 is None:
-                    x.zero_()
-                elif x.data_ptr() != x0.data_ptr():
-                    x.copy_(x0)
-            if n == 0:
-                return SolveResult(x, 0, True, "converged", 0.0, 0.0, 0)
-            control, r, rhat, p, v, t, y, z, inv = self._workspace(dev)
-            control.upload(self.rtol, self.atol, self.maxiter)
-            a = bicgstab.Params()
-            a.cg = op.args(dev, tangent, control)
-            a.cg.b, a.cg.x, a.cg.r, a.cg.z, a.cg.p, a.cg.inv = (w.data_ptr() for w in (b, x, r, z, p, inv))
-            a.rhat, a.v, a.t, a.y = (w.data_ptr() for w in (rhat, v, t, y))
-            a.cg.has_x0 = 0 if x0 is None else 1
-            code, cap, blocks = self._code, BLOCKS_PER_CU * jit.num_cu(dev), op.blocks(dev)
-            ml = self._ml
-            tangent_ptr = tangent.data_ptr()
-            if ml is not None:  # (the preconditioner forms the blocks and level 1 from the tangent)
-                ml._setup(dev, tangent, control)
-            elif self._kind == 1:  # the nodes' own blocks without a matrix: a BSR values array over the diagonal pattern
-                a.cg.values = A.diagonal_blocks(tangent, out=self._diagonal_blocks(dev)).data_ptr()
-                jit.launch(code, dev, max(1, min(-(-A.n_nodes // 256), cap)), a.cg, "MatrixFreeBiCGStab inverse launch", kernel=solver.INVERSE_KERNEL)
-                a.cg.values = tangent_ptr
-            a.cg.q = v.data_ptr()
-            if x0 is not None:  # A x0 into v, by the operator's quiet product
-                A._apply(dev, tangent_ptr, x.data_ptr(), v.data_ptr(), MODE_QUIET)
-            jit.launch(code, dev, blocks, a, "MatrixFreeBiCGStab start launch", kernel=bicgstab.START_KERNEL)
-            direction_blocks = max(1, min(-(-n // bicgstab._CHUNK) if self._kind == 1 else -(-(n // 2) // 256), cap))
-            launch = self._product.launch
-
-            control.download(dev)  # a solve that ends at its start (b = 0, a singular block, maxiter = 0) enqueues no iteration
-            looks = 1
-            while int(control.ints[solver._STATUS]) == 0:
-                for _ in range(self.check_every):
-                    if ml is not None:
-                        ml._cycle(dev, tangent, control, p.data_ptr(), y.data_ptr())
-                    launch(dev, tangent_ptr, y.data_ptr(), v.data_ptr(), rhat.data_ptr(), DOT_V, control)
-                    jit.launch(code, dev, blocks, a, "MatrixFreeBiCGStab half-step launch", kernel=bicgstab.HALF_KERNEL)
-                    if ml is not None:
-                        ml._cycle(dev, tangent, control, r.data_ptr(), z.data_ptr())
-                    launch(dev, tangent_ptr, z.data_ptr(), t.data_ptr(), r.data_ptr(), DOT_T, control)
-                    jit.launch(code, dev, blocks, a, "MatrixFreeBiCGStab full-step launch", kernel=bicgstab.FULL_KERNEL)
-                    jit.launch(code, dev, direction_blocks, a, "MatrixFreeBiCGStab direction launch", kernel=bicgstab.DIRECTION_KERNEL)
-                control.download(dev)
-                looks += 1
-            h, status = control.host, int(control.ints[solver._STATUS])
-            return SolveResult(x, int(control.ints[solver._ITERATIONS]), status == 1, STATUSES[status], float(np.sqrt(h[solver._RR])),
-                               float(np.sqrt(h[solver._BB])), looks)
+        return product

@@ -84,6 +84,16 @@ def kernel_resources(log: str, kernel: str) -> dict:
     raise RuntimeError(f"no resource remarks for {kernel} in the compile log")
 
 
+def compile_without_scratch(text: str, name: str, entry: str, kernels):
+    """``jit.compile_program(text, name, entry)``; one of ``kernels`` with scratch is a ``ValueError`` that names it"""
+    code = jit.compile_program(text, name, entry)
+    for kernel in kernels:
+        scratch = kernel_resources(code.log, kernel)["scratch_bytes"]
+        if scratch:
+            raise ValueError(f"{name}: {kernel} compiles with {scratch} bytes of scratch per lane")
+    return code
+
+
 def compile_kernels(gdim: int, nodes_per_cell: int, points_per_cell: int, affine: bool, layout: str = "nabla_grad", source: str = "stress",
                     accumulate: bool = False, waves: int | None = None):
     """The code object of one shape, both kernels in it (no GPU needed).  ``waves``: that register budget of the element kernel;

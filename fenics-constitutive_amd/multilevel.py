@@ -104,7 +104,7 @@ import numpy as np
 
 from . import jit, solver
 from . import matrix as _matrix
-from .force import kernel_resources
+from .force import compile_without_scratch, kernel_resources
 from .gradient import BLOCKS_PER_CU
 from .matrix import TangentMatrix
 from .tangent_operator import TangentOperator
@@ -155,12 +155,7 @@ def compile_kernels(gdim: int):
     """The code object of one block size, all ten kernels in it (no GPU needed).  A kernel with scratch is a ``ValueError``."""
     if gdim not in (1, 2, 3):
         raise ValueError(f"the dofs per node must be 1, 2 or 3, got {gdim}")
-    code = jit.compile_program(program(gdim), f"multilevel_{gdim}d", solver.MATVEC_KERNEL)
-    for kernel in solver.KERNELS + KERNELS:
-        scratch = kernel_resources(code.log, kernel)["scratch_bytes"]
-        if scratch:
-            raise ValueError(f"multilevel_{gdim}d: {kernel} compiles with {scratch} bytes of scratch per lane")
-    return code
+    return compile_without_scratch(program(gdim), f"multilevel_{gdim}d", solver.MATVEC_KERNEL, solver.KERNELS + KERNELS)
 
 
 def coarse_dofs(gdim: int) -> int:
@@ -180,16 +175,8 @@ def compile_rigid_kernels(gdim: int):
     needed).  A kernel with scratch is a ``ValueError``."""
     if gdim not in (2, 3):
         raise ValueError(f"the rigid-body coarse space is for 2 or 3 dofs per node, got {gdim}")
-    codes = []
-    for block in (gdim, coarse_dofs(gdim)):
-        name = f"multilevel_rigid_{gdim}d_{block}"
-        code = jit.compile_program(rigid_program(gdim, block), name, solver.MATVEC_KERNEL)
-        for kernel in solver.KERNELS + KERNELS + RIGID_KERNELS:
-            scratch = kernel_resources(code.log, kernel)["scratch_bytes"]
-            if scratch:
-                raise ValueError(f"{name}: {kernel} compiles with {scratch} bytes of scratch per lane")
-        codes.append(code)
-    return tuple(codes)
+    return tuple(compile_without_scratch(rigid_program(gdim, block), f"multilevel_rigid_{gdim}d_{block}", solver.MATVEC_KERNEL,
+                                         solver.KERNELS + KERNELS + RIGID_KERNELS) for block in (gdim, coarse_dofs(gdim)))
 
 
 def free_program(gdim: int, nodes_per_cell: int) -> str:
@@ -204,12 +191,8 @@ def compile_free_kernels(gdim: int, nodes_per_cell: int):
         raise ValueError(f"the dofs per node must be 1, 2 or 3, got {gdim}")
     if nodes_per_cell < 1:
         raise ValueError("a cell needs at least one node")
-    name = f"multilevel_free_{gdim}d_{nodes_per_cell}n"
-    code = jit.compile_program(free_program(gdim, nodes_per_cell), name, FREE_GALERKIN_KERNEL)
-    scratch = kernel_resources(code.log, FREE_GALERKIN_KERNEL)["scratch_bytes"]
-    if scratch:
-        raise ValueError(f"{name}: {FREE_GALERKIN_KERNEL} compiles with {scratch} bytes of scratch per lane")
-    return code
+    return compile_without_scratch(free_program(gdim, nodes_per_cell), f"multilevel_free_{gdim}d_{nodes_per_cell}n", FREE_GALERKIN_KERNEL,
+                                   (FREE_GALERKIN_KERNEL,))
 
 
 def free_rigid_program(gdim: int, nodes_per_cell: int) -> str:
@@ -224,12 +207,8 @@ def compile_free_rigid_kernels(gdim: int, nodes_per_cell: int):
         raise ValueError(f"the rigid-body coarse space is for 2 or 3 dofs per node, got {gdim}")
     if nodes_per_cell < 1:
         raise ValueError("a cell needs at least one node")
-    name = f"multilevel_free_rigid_{gdim}d_{nodes_per_cell}n"
-    code = jit.compile_program(free_rigid_program(gdim, nodes_per_cell), name, FREE_RIGID_GALERKIN_KERNEL)
-    scratch = kernel_resources(code.log, FREE_RIGID_GALERKIN_KERNEL)["scratch_bytes"]
-    if scratch:
-        raise ValueError(f"{name}: {FREE_RIGID_GALERKIN_KERNEL} compiles with {scratch} bytes of scratch per lane")
-    return code
+    return compile_without_scratch(free_rigid_program(gdim, nodes_per_cell), f"multilevel_free_rigid_{gdim}d_{nodes_per_cell}n",
+                                   FREE_RIGID_GALERKIN_KERNEL, (FREE_RIGID_GALERKIN_KERNEL,))
 
 
 # ---- the hierarchy (host) --------------------------------------------------------------------------------------------------------
@@ -366,9 +345,9 @@ class FreeRigidArgs(C.Structure):
 
 
 # ---- the seam of level 0 -----------------------------------------------------------------------------------------------------------
-# What the preconditioner asks of its fine level, and nothing else reads ``K``: the pattern the hierarchy is built from, the check of
-# the first argument of a call, the array the inverse kernel reads the nodes' own blocks from, the launches of a product, the first
-# Galerkin step, and the device pointers of all that a cached launch plan holds.
+# What the preconditioner alone asks of its fine level: the pattern the hierarchy is built from, the launches of a product, the first
+# Galerkin step, and the device pointers of all that a cached launch plan holds.  The check of the first argument of a call, the node
+# without a diagonal block and the array the inverse kernel reads the nodes' own blocks from are the solver's seam's (``solver._Seam``).
 class _AssembledFine:
     """level 0 is a ``TangentMatrix``: its values array is read where ``dest_base`` / ``dest_stride`` say"""
 
@@ -377,14 +356,6 @@ class _AssembledFine:
     def __init__(self, K: TangentMatrix):
         self.K = K
         self.indptr, self.indices = K.indptr, K.indices
-        self.missing = np.flatnonzero(K.diag_block < 0)
-
-    def check(self, values, dev: int) -> None:
-        self.K._check("values", values, self.K.nnz, dev)
-
-    def blocks(self, pc, dev: int, values) -> int:
-        """the pointer the inverse kernel of level 0 reads through the operator's diagonal table: the values themselves"""
-        return values.data_ptr()
 
     def product(self, pc, dev: int, values, control, x_ptr: int, q_ptr: int, cap: int) -> list:
         a = pc._level_args(dev, 0, values, control)
@@ -417,7 +388,6 @@ class _FreeFine:
         unused = np.flatnonzero(A.valence == 0).astype(np.int32)
         cells = A.op._dofmap if not unused.size else np.concatenate([A.op._dofmap, np.repeat(unused[:, None], a_, axis=1)])
         self.indptr, self.indices = _matrix.block_pattern(cells, A.n_nodes)
-        self.missing = np.zeros(0, dtype=np.int64)
         self.element_code = self.gather_code = None
         self.blk_ptr = self.contributions = self.block_row = None
         self.chunk_blocks = []
@@ -443,14 +413,6 @@ class _FreeFine:
             block_of[self.contributions] = np.repeat(np.arange(coarse.nnzb, dtype=np.int32), np.diff(self.blk_ptr))
             starts = np.arange(0, A.n_cells, self.chunk_cells, dtype=np.int64) * (a_ * a_)
             self.chunk_blocks = list(zip(np.minimum.reduceat(block_of, starts).tolist(), (np.maximum.reduceat(block_of, starts) + 1).tolist()))
-
-    def check(self, tangent, dev: int) -> None:
-        self.K._check("tangent", tangent, self.K.tangent_dim * self.K.n_points, dev)
-
-    def blocks(self, pc, dev: int, tangent) -> int:
-        """the nodes' own blocks, formed now by the operator's two diagonal kernels (asynchronous): a BSR values array over the
-        diagonal pattern, which is what the operator's diagonal table ``0 .. n`` makes of it"""
-        return self.K.diagonal_blocks(tangent, out=pc._device(dev).blocks).data_ptr()
 
     def product(self, pc, dev: int, tangent, control, x_ptr: int, q_ptr: int, cap: int) -> list:
         # (quiet mode neither reads nor writes the control block: a product enqueued behind the end of a solve writes the
@@ -546,6 +508,7 @@ class _OnDevice:
             self.tables.append(t)
             self.inv.append(zeros(dofs[l]**2 * lv.n_nodes))
             self.q.append(zeros(dofs[l] * lv.n_nodes))
+        self.blocks = None  # (a matrix has its nodes' own blocks in its values)
         if pc._seam.free:  # the nodes' own blocks of level 0 and, with a coarse level, the element matrices of a chunk of cells
             A, seam = pc.K, pc._seam
             self.blocks = zeros(A.gdim**2 * A.n_nodes)[: A.gdim**2 * A.n_nodes]
@@ -621,8 +584,9 @@ class MultilevelPreconditioner:
             if v < 1 or v >= 2**31:
                 raise ValueError(f"{name} must lie in [1, 2^31), got {v}")
         seam = _FreeFine(K) if isinstance(K, TangentOperator) else _AssembledFine(K)  # (an operator: raises the ValueError of its scratch)
-        if seam.missing.size:
-            raise ValueError(f"node {int(seam.missing[0])} has no diagonal block in the pattern: its row is empty, the matrix singular")
+        self._op = solver._operator(K)
+        if not seam.free:  # (an operator's node of no cell has a row of its own block in the pattern, and a zero block at setup)
+            self._op.refuse_missing()
         self.K = K
         self._seam = seam
         # fixed for the life of the object (read-only properties below): the launch plan of a cycle is built from them
@@ -642,7 +606,6 @@ class MultilevelPreconditioner:
                 _refuse_degenerate(self._levels[0])
         #: dofs per node, by level
         self._dofs = [K.gdim] + [coarse_dofs(K.gdim) if self._rigid else K.gdim] * (len(self._levels) - 1)
-        self._op = solver._operator(K)
         if self._rigid:
             self._code, self._coarse_code = compile_rigid_kernels(K.gdim)
         else:
@@ -811,7 +774,7 @@ class MultilevelPreconditioner:
         for l, lv in enumerate(self._levels):
             a = self._level_args(dev, l, values, control)
             if l == 0:  # (a matrix: its values; an operator: the block array its diagonal kernels fill here)
-                a.values = self._seam.blocks(self, dev, values)
+                a.values = self._op.own_blocks(dev, values, on.blocks)
             jit.launch(self._program(l), dev, self._blocks(lv.n_nodes, cap), a, "MultilevelPreconditioner inverse launch", kernel=solver.INVERSE_KERNEL)
 
     def _plan(self, dev: int, values, control, r_ptr: int, z_ptr: int) -> list:
@@ -924,7 +887,7 @@ class MultilevelPreconditioner:
         import torch
 
         dev = self.device
-        self._seam.check(values, dev)
+        self._op.check(values, dev)
         with torch.cuda.device(dev):
             if self.K.shape[0]:
                 self._setup(dev, values, self._own_control(dev))
@@ -937,7 +900,7 @@ class MultilevelPreconditioner:
         import torch
 
         dev, n = self.device, self.K.shape[0]
-        self._seam.check(values, dev)
+        self._op.check(values, dev)
         self.K._check("r", r, n, dev)
         if out is not None:
             self.K._check("out", out, n, dev)

@@ -57,6 +57,13 @@ instance built on the same operator, ``MultilevelPreconditioner(A)`` (program ``
 fine matrix, its first coarse level is gathered from the element matrices (``multilevel.py``).  The string form "multilevel" builds
 the preconditioner of a matrix and stays refused with an operator.
 
+*The seam and the driver.*  What differs between a matrix and an operator is in ``_Operator`` and ``_FreeOperator`` (base ``_Seam``: the
+check of a call's first argument, the node without a block of its own, the device tables, the product, the array the inverse kernel
+reads the nodes' own blocks from); nothing else in the solvers or in ``multilevel.py`` asks which of the two ``K`` is.  What every
+Krylov solver does on the host -- the validation of the options, the prelude of a call, the inverses, the loop of looks and batches,
+the ``SolveResult`` -- is ``_Krylov``, once; ``ConjugateGradient`` here and ``bicgstab._BiCGStab`` supply a workspace, the start and "enqueue
+one iteration" ("One Krylov driver").
+
 LDS of a block: ``lds_bytes(kernel)``; the same ``LDS_CAP`` as the other operators.
 """
 
@@ -68,7 +75,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import jit
-from .force import kernel_resources
+from .force import compile_without_scratch, kernel_resources
 from .gradient import BLOCKS_PER_CU, LDS_CAP
 from .matrix import TangentMatrix
 from .tangent_operator import MODE_QUIET as _MODE_QUIET
@@ -122,12 +129,7 @@ def compile_kernels(gdim: int, preconditioned: bool, slab: int = SLAB):
         raise ValueError(f"the slab must be a positive multiple of 128 doubles, got {slab}")
     if lds_bytes(MATVEC_KERNEL, slab=slab) > LDS_CAP:
         raise ValueError(f"four wave regions of {slab} doubles need {lds_bytes(MATVEC_KERNEL, slab=slab)} bytes of LDS per block; at most {LDS_CAP} fit")
-    code = jit.compile_program(program(gdim, preconditioned, slab), f"conjugate_gradient_{gdim}d", MATVEC_KERNEL)
-    for kernel in KERNELS:
-        scratch = kernel_resources(code.log, kernel)["scratch_bytes"]
-        if scratch:
-            raise ValueError(f"conjugate_gradient_{gdim}d: {kernel} compiles with {scratch} bytes of scratch per lane")
-    return code
+    return compile_without_scratch(program(gdim, preconditioned, slab), f"conjugate_gradient_{gdim}d", MATVEC_KERNEL, KERNELS)
 
 
 class Args(C.Structure):
@@ -158,14 +160,14 @@ def _segments(n: int) -> int:
 
 
 class _Control:
-    """the control block of one device: the device copy, the page-locked host copy and the partial sums"""
+    """the control block of one device, ``scalars`` doubles of it: the device copy, the page-locked host copy and the partial sums"""
 
-    def __init__(self, dev: int, nseg: int):
+    def __init__(self, dev: int, nseg: int, scalars: int = _SCALARS):
         import torch
 
         d = torch.device("cuda", dev)
-        self.device_block = torch.zeros(_SCALARS, dtype=torch.float64, device=d)
-        self.pinned = torch.zeros(_SCALARS, dtype=torch.float64).pin_memory()
+        self.device_block = torch.zeros(scalars, dtype=torch.float64, device=d)
+        self.pinned = torch.zeros(scalars, dtype=torch.float64).pin_memory()
         self.host = self.pinned.numpy()
         self.ints = self.host.view(np.int32)
         self.partials = torch.zeros(3 * max(nseg, 1), dtype=torch.float64, device=d)
@@ -186,10 +188,53 @@ class _Control:
         torch.cuda.current_stream(dev).synchronize()
 
 
-class _Operator:
-    """The seam the solver applies ``K`` through: the assembled matrix of a ``TangentMatrix`` -- its pattern tables on the device,
-    ``q = K p`` with ``p . q`` behind it.  One per matrix, kept on the matrix object (``_operator``), so the tables are uploaded once
-    and go with the matrix.  (A matrix-free operator would be another class with the same ``apply``.)"""
+class _Seam:
+    """What the solvers and the multilevel preconditioner ask of ``K`` and nothing else reads it for: the check of a call's first
+    argument, the nodes without a block of their own, the tables on the device, ``q = K p`` with ``p . q`` behind it, the array the
+    inverse kernel reads the nodes' own blocks from, and the control block of the plain product.  One per matrix or operator, kept on
+    that object (``_operator``), so the tables are uploaded once and go with it.  A class gives ``first`` and ``first_numel`` (the name
+    and length of the first argument), ``other`` (the refusal of a preconditioner built on another object), ``by_name`` (whether
+    ``preconditioner="multilevel"`` can build one), ``block_numel`` (the entries of the ``out`` of ``own_blocks``, 0: it needs none),
+    ``_host_tables``, ``args``, ``apply``, ``refuse_missing`` and ``own_blocks``."""
+
+    def __init__(self, K, n: int):
+        self.matrix, self.gdim, self.n, self.n_nodes = K, K.gdim, n, K.n_nodes
+        self.nseg = _segments(n)
+        self._on = {}  # device index -> the tables of _host_tables
+        self._control = {}  # device index -> _Control (of the plain product)
+
+    def check(self, values, dev: int) -> None:
+        """the first argument of a call: a float64 tensor of ``first_numel`` entries on the device"""
+        self.matrix._check(self.first, values, self.first_numel, dev)
+
+    def tables(self, dev: int):
+        t = self._on.get(dev)
+        if t is None:
+            import torch
+
+            from .hostio import to_device
+
+            d = torch.device("cuda", dev)
+            with torch.cuda.device(d):
+                t = self._on[dev] = tuple(to_device(x, d) for x in self._host_tables())
+        return t
+
+    def control(self, dev: int) -> _Control:
+        c = self._control.get(dev)
+        if c is None:
+            c = self._control[dev] = _Control(dev, self.nseg)
+        return c
+
+    def blocks(self, dev: int) -> int:
+        """blocks of a launch over the segments: looked up on ``jit`` at launch"""
+        return max(1, min(self.nseg, BLOCKS_PER_CU * jit.num_cu(dev)))
+
+
+class _Operator(_Seam):
+    """the seam of a ``TangentMatrix``: the assembled matrix, its values array the first argument of every call"""
+
+    first, by_name, block_numel = "values", True, 0
+    other = "the MultilevelPreconditioner was built for another matrix"
 
     def __init__(self, matrix: TangentMatrix):
         d_ = matrix.gdim
@@ -204,28 +249,21 @@ class _Operator:
             base, stride = dd * k0 + d_ * (k - k0), d_ * per_row[matrix.block_row]
         if not (np.array_equal(base, matrix.dest_base) and np.array_equal(stride, matrix.dest_stride)):
             raise ValueError(f"the values of format {matrix.format!r} are not where the solver's kernels look for them")
-        self.matrix, self.gdim = matrix, d_
-        self.n, self.nnz, self.n_nodes = d_ * matrix.n_nodes, matrix.nnz, matrix.n_nodes
-        self.nseg = _segments(self.n)
+        super().__init__(matrix, d_ * matrix.n_nodes)
+        self.nnz = self.first_numel = matrix.nnz
         self.csr = 1 if matrix.format == "csr" else 0
-        self._on = {}  # device index -> (indptr, indices, diag, groups)
-        self._control = {}  # device index -> _Control (of the plain product)
 
-    def tables(self, dev: int):
-        t = self._on.get(dev)
-        if t is None:
-            import torch
+    def refuse_missing(self) -> None:
+        missing = np.flatnonzero(self.matrix.diag_block < 0)
+        if missing.size:
+            raise ValueError(f"node {int(missing[0])} has no diagonal block in the pattern: its row is empty, the matrix singular")
 
-            from .hostio import to_device
-
-            d = torch.device("cuda", dev)
-            m = self.matrix
-            with torch.cuda.device(d):
-                # scalar CSR: the node of the columns of every run of D values (the rows of a block are apart there)
-                groups = (m.csr_indices[:: self.gdim] // self.gdim).astype(np.int32) if self.csr and m.nnzb else np.zeros(1, dtype=np.int32)
-                t = self._on[dev] = tuple(to_device(x, d) for x in (m.indptr, m.indices if m.nnzb else np.zeros(1, dtype=np.int32),
-                                                                    np.maximum(m.diag_block, 0).astype(np.int32), groups))
-        return t
+    def _host_tables(self):
+        """(indptr, indices, diag, groups)"""
+        m = self.matrix
+        # scalar CSR: the node of the columns of every run of D values (the rows of a block are apart there)
+        groups = (m.csr_indices[:: self.gdim] // self.gdim).astype(np.int32) if self.csr and m.nnzb else np.zeros(1, dtype=np.int32)
+        return m.indptr, m.indices if m.nnzb else np.zeros(1, dtype=np.int32), np.maximum(m.diag_block, 0).astype(np.int32), groups
 
     def args(self, dev: int, values, control: _Control) -> Args:
         indptr, indices, diag, groups = self.tables(dev)
@@ -235,41 +273,41 @@ class _Operator:
         a.n, a.nnz, a.nseg, a.n_nodes, a.csr = self.n, self.nnz, self.nseg, self.n_nodes, self.csr
         return a
 
-    def blocks(self, dev: int) -> int:
-        """blocks of a launch over the segments: looked up on ``jit`` at launch"""
-        return max(1, min(self.nseg, BLOCKS_PER_CU * jit.num_cu(dev)))
+    def own_blocks(self, dev: int, values, out) -> int:
+        """the pointer the inverse kernel reads the nodes' own blocks from, through the diagonal table: the values themselves
+        (``out`` is not used)"""
+        return values.data_ptr()
 
     def apply(self, code, dev: int, a: Args, vector_ptr: int, out_ptr: int, mode: int) -> None:
         """``out = K vector`` and the ordered ``vector . out`` (``_MODE_ITERATE``: into ``pq``, under the status; ``_MODE_PLAIN``: into ``dot``)
-        by the matrix-vector kernel of ``code``"""
+        by the matrix-vector kernel of ``code`` (``None``: of the program without a preconditioner)"""
         a.va, a.q, a.mode = vector_ptr, out_ptr, mode
-        jit.launch(code, dev, self.blocks(dev), a, "ConjugateGradient matrix-vector launch", kernel=MATVEC_KERNEL)
+        jit.launch(code or _plain_code(self.gdim), dev, self.blocks(dev), a, "ConjugateGradient matrix-vector launch", kernel=MATVEC_KERNEL)
 
 
-class _FreeOperator:
-    """The seam for a ``TangentOperator``: ``q = A p`` with ``p . q`` behind it by the operator's own two kernels, from the tangent of
-    the quadrature points (``values`` is that tangent here).  The block array the inverse kernel reads is a BSR values array whose
+class _FreeOperator(_Seam):
+    """The seam of a ``TangentOperator``: ``q = A p`` with ``p . q`` behind it by the operator's own two kernels, from the tangent of
+    the quadrature points, the first argument of every call.  The block array the inverse kernel reads is a BSR values array whose
     pattern is the diagonal: ``indptr`` and the diagonal table are both ``0 .. n``, one table on the device."""
 
+    first, by_name = "tangent", False
+    other = ("the MultilevelPreconditioner was built for another object: the multilevel preconditioner of a TangentOperator A is "
+             "MultilevelPreconditioner(A), built on this very operator")
+
     def __init__(self, operator: TangentOperator):
-        self.matrix, self.gdim = operator, operator.gdim
-        self.n, self.nnz, self.n_nodes = operator.shape[0], 0, operator.n_nodes
-        self.nseg = _segments(self.n)
-        self.csr = 0
-        self._on = {}  # device index -> (0 .. n_nodes as int32,)
-        self._control = {}  # device index -> _Control (of the plain product)
+        super().__init__(operator, operator.shape[0])
+        self.nnz, self.csr = 0, 0
+        self.first_numel = operator.tangent_dim * operator.n_points
+        self.block_numel = self.gdim**2 * self.n_nodes
 
-    def tables(self, dev: int):
-        t = self._on.get(dev)
-        if t is None:
-            import torch
+    def refuse_missing(self) -> None:
+        missing = np.flatnonzero(self.matrix.valence == 0)
+        if missing.size:
+            raise ValueError(f"node {int(missing[0])} belongs to no cell: it has no diagonal block, its row is empty, the matrix singular")
 
-            from .hostio import to_device
-
-            d = torch.device("cuda", dev)
-            with torch.cuda.device(d):
-                t = self._on[dev] = (to_device(np.arange(self.n_nodes + 1, dtype=np.int32), d),)
-        return t
+    def _host_tables(self):
+        """(0 .. n_nodes as int32,)"""
+        return (np.arange(self.n_nodes + 1, dtype=np.int32),)
 
     def args(self, dev: int, tangent, control: _Control) -> Args:
         (count,) = self.tables(dev)
@@ -280,8 +318,10 @@ class _FreeOperator:
         a.values = tangent.data_ptr()  # (the inverse kernel is launched with the block array in its place)
         return a
 
-    def blocks(self, dev: int) -> int:
-        return max(1, min(self.nseg, BLOCKS_PER_CU * jit.num_cu(dev)))
+    def own_blocks(self, dev: int, tangent, out) -> int:
+        """the nodes' own blocks, formed now into ``out``, the caller's ``[n_nodes][D][D]``, by the operator's two diagonal kernels
+        (asynchronous): a BSR values array over the diagonal pattern, which is what the table ``0 .. n`` makes of it"""
+        return self.matrix.diagonal_blocks(tangent, out=out).data_ptr()
 
     def apply(self, code, dev: int, a: Args, vector_ptr: int, out_ptr: int, mode: int) -> None:
         """``out = A vector`` and the ordered ``vector . out`` by the operator's kernels (``code``, the solver's program, is not used)"""
@@ -312,55 +352,26 @@ def _operator(matrix: TangentMatrix) -> _Operator:
 
 def matvec(K: TangentMatrix, values, p, out=None):
     """``out = K p`` by the solver's matrix-vector kernel (asynchronous, on torch's current stream): ``values`` the array ``K``
-    wrote, ``p`` and ``out`` float64 device tensors of ``D n_nodes`` entries.  A row without blocks is ``+0.0``."""
+    wrote, ``p`` and ``out`` float64 device tensors of ``D n_nodes`` entries.  A row without blocks is ``+0.0``.  With a
+    ``TangentOperator`` ``values`` is the tangent of the quadrature points and the product the operator's own.  The ordered
+    ``p . out`` is left in the ``dot`` of the control block the seam keeps."""
     import torch
 
-    if isinstance(K, TangentOperator):
-        return _free_matvec(K, values, p, out)
-    if not isinstance(K, TangentMatrix):
+    if not isinstance(K, (TangentMatrix, TangentOperator)):
         raise TypeError(f"K must be a TangentMatrix, got {type(K).__name__}")
-    dev = K.device
-    n = K.shape[0]
-    K._check("values", values, K.nnz, dev)
+    op = _operator(K)
+    dev, n = K.device, op.n
+    op.check(values, dev)
     K._check("p", p, n, dev)
     if out is not None:
         K._check("out", out, n, dev)
         if _overlap(out, p):
             raise ValueError("out must not alias p")
-    op = _operator(K)
     with torch.cuda.device(dev):
         if out is None:
             out = torch.empty(n, dtype=torch.float64, device=torch.device("cuda", dev))
-        if n == 0:
-            return out
-        control = op._control.get(dev)
-        if control is None:
-            control = op._control[dev] = _Control(dev, op.nseg)
-        op.apply(_plain_code(K.gdim), dev, op.args(dev, values, control), p.data_ptr(), out.data_ptr(), _MODE_PLAIN)
-    return out
-
-
-def _free_matvec(A: TangentOperator, tangent, p, out=None):
-    """``matvec`` for a ``TangentOperator``: ``out = A p`` from ``tangent`` in ``_MODE_PLAIN`` -- the ordered ``p . out`` is left in the ``dot``
-    of the control block the operator's seam keeps (asynchronous, on torch's current stream)"""
-    import torch
-
-    dev = A.device
-    n = A.shape[0]
-    A._check("tangent", tangent, A.tangent_dim * A.n_points, dev)
-    A._check("p", p, n, dev)
-    if out is not None:
-        A._check("out", out, n, dev)
-        if _overlap(out, p):
-            raise ValueError("out must not alias p")
-    op = _operator(A)
-    with torch.cuda.device(dev):
-        if out is None:
-            out = torch.empty(n, dtype=torch.float64, device=torch.device("cuda", dev))
-        control = op._control.get(dev)
-        if control is None:
-            control = op._control[dev] = _Control(dev, op.nseg)
-        op.apply(None, dev, op.args(dev, tangent, control), p.data_ptr(), out.data_ptr(), _MODE_PLAIN)
+        if n:
+            op.apply(None, dev, op.args(dev, values, op.control(dev)), p.data_ptr(), out.data_ptr(), _MODE_PLAIN)
     return out
 
 
@@ -407,7 +418,127 @@ def _overlap(a, b) -> bool:
     return a0 < b0 + 8 * b.numel() and b0 < a0 + 8 * a.numel()
 
 
-class ConjugateGradient:
+class _Krylov:
+    """The host side of a Krylov solver on the seam, written once: the validation of the options, the prelude of a call (the checks
+    of the tensors, the alias rules, ``x`` from ``x0`` / ``out``, the empty system), the block array of an operator's block-Jacobi, the
+    inverses a preconditioner applies, and the loop of uploads, looks and batches that ends in a ``SolveResult``.  A subclass sets
+    ``_code``, the code object the inverse kernel is launched from, and supplies ``_workspace(dev)``, the tuple of the control block and
+    its vectors, and ``_start(dev, values, b, x, has_x0, work)``, which enqueues everything up to the first look and returns the
+    function that enqueues one iteration."""
+
+    _STATUSES = STATUSES
+
+    def __init__(self, K, preconditioner, rtol, atol, maxiter, check_every):
+        from .multilevel import MultilevelPreconditioner
+
+        op = _operator(K)
+        named = isinstance(preconditioner, str) and preconditioner == "multilevel"
+        if named and not op.by_name:
+            raise ValueError('preconditioner="multilevel" builds the multilevel preconditioner of a matrix: with a TangentOperator A pass the instance, '
+                             f"MultilevelPreconditioner(A), or one of {PRECONDITIONERS}")
+        if isinstance(preconditioner, MultilevelPreconditioner):
+            if preconditioner.K is not K:
+                raise ValueError(op.other)
+        elif not (named or preconditioner is None or (isinstance(preconditioner, str) and preconditioner == "block_jacobi")):
+            names = PRECONDITIONERS + (("multilevel",) if op.by_name else ())
+            raise ValueError(f"preconditioner must be one of {names} or a MultilevelPreconditioner of K, got {preconditioner!r}")
+        for name, v in (("rtol", rtol), ("atol", atol)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise TypeError(f"{name} must be a number, got {type(v).__name__}")
+            if not (v >= 0.0 and np.isfinite(v)):
+                raise ValueError(f"{name} must be finite and not negative, got {v}")
+        if maxiter is None:
+            maxiter = 10 * op.n
+        for name, v, least in (("maxiter", maxiter, 0), ("check_every", check_every, 1)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{name} must be an integer, got {type(v).__name__}")
+            if v < least or v >= 2**31:
+                raise ValueError(f"{name} must lie in [{least}, 2^31), got {v}")
+        op.refuse_missing()
+        if named:  # (once everything else has been validated)
+            preconditioner = MultilevelPreconditioner(K)
+        self.K = K
+        self.preconditioner = preconditioner
+        self.rtol, self.atol, self.maxiter, self.check_every = float(rtol), float(atol), int(maxiter), int(check_every)
+        self._op = op
+        #: the multilevel preconditioner (its cycle runs on this solver's control block), or None
+        self._ml = preconditioner if isinstance(preconditioner, MultilevelPreconditioner) else None
+        self.n = op.n
+        self._name = type(self).__name__  # of the launches, in ``jit.launch``'s errors
+        self._work = {}  # device index -> _workspace(dev)
+        self._work_blocks = {}  # device index -> the block array of a TangentOperator's block-Jacobi
+
+    @property
+    def compile_log(self) -> str:
+        return self._code.log
+
+    @property
+    def device(self) -> int:
+        return self.K.device
+
+    def _diagonal_blocks(self, dev: int):
+        """the block array of a ``TangentOperator``'s block-Jacobi, ``[n_nodes][D][D]``, one per device (a matrix needs none)"""
+        blocks = self._work_blocks.get(dev)
+        if blocks is None and self._op.block_numel:
+            import torch
+
+            blocks = self._work_blocks[dev] = torch.zeros(self._op.block_numel, dtype=torch.float64, device=torch.device("cuda", dev))
+        return blocks
+
+    def _inverses(self, dev: int, values, a: Args, control: _Control) -> None:
+        """what the preconditioner applies, formed from ``values``: the multilevel setup, or the inverses of the nodes' own blocks by the
+        inverse kernel of ``_code`` on ``a``, or nothing"""
+        if self._ml is not None:  # (on an operator ``values`` is the tangent: the preconditioner forms the blocks and level 1 from it)
+            self._ml._setup(dev, values, control)
+        elif self.preconditioner:
+            a.values = self._op.own_blocks(dev, values, self._diagonal_blocks(dev))
+            jit.launch(self._code, dev, max(1, min(-(-self._op.n_nodes // 256), BLOCKS_PER_CU * jit.num_cu(dev))), a, f"{self._name} inverse launch",
+                       kernel=INVERSE_KERNEL)
+            a.values = values.data_ptr()
+
+    def __call__(self, values, b, x0=None, out=None) -> SolveResult:
+        """solve ``K x = b`` (synchronous at its end); with a ``TangentOperator`` the first argument is the tangent of the quadrature
+        points"""
+        import torch
+
+        K, dev, n = self.K, self.device, self.n
+        self._op.check(values, dev)
+        K._check("b", b, n, dev)
+        if x0 is not None:
+            K._check("x0", x0, n, dev)
+        if out is not None:
+            K._check("out", out, n, dev)
+            if _overlap(out, b):
+                raise ValueError("out must not alias b")
+            if x0 is not None and _overlap(out, x0) and out.data_ptr() != x0.data_ptr():
+                raise ValueError("out may be x0 itself, not a part of it")
+        with torch.cuda.device(dev):
+            if out is None:
+                x = torch.zeros(n, dtype=torch.float64, device=torch.device("cuda", dev)) if x0 is None else x0.clone()
+            else:
+                x = out
+                if x0 is None:
+                    x.zero_()
+                elif x.data_ptr() != x0.data_ptr():
+                    x.copy_(x0)
+            if n == 0:
+                return SolveResult(x, 0, True, "converged", 0.0, 0.0, 0)
+            work = self._workspace(dev)
+            control = work[0]
+            control.upload(self.rtol, self.atol, self.maxiter)
+            iterate = self._start(dev, values, b, x, x0 is not None, work)
+            control.download(dev)  # a solve that ends at its start (b = 0, a singular block, maxiter = 0) enqueues no iteration
+            looks = 1
+            while int(control.ints[_STATUS]) == 0:
+                for _ in range(self.check_every):
+                    iterate()
+                control.download(dev)
+                looks += 1
+            h, status = control.host, int(control.ints[_STATUS])
+            return SolveResult(x, int(control.ints[_ITERATIONS]), status == 1, self._STATUSES[status], float(np.sqrt(h[_RR])), float(np.sqrt(h[_BB])), looks)
+
+
+class ConjugateGradient(_Krylov):
     """``cg(values, b, x0=None, out=None) -> SolveResult``: ``K x = b`` by preconditioned conjugate gradients on the GPU.
 
     ``K``: the ``TangentMatrix`` whose values array is solved with, in either format.  ``preconditioner``: "block_jacobi" -- the
@@ -433,59 +564,12 @@ class ConjugateGradient:
 
     def __init__(self, K: TangentMatrix, preconditioner="block_jacobi", rtol: float = 1e-8, atol: float = 0.0, maxiter: int | None = None,
                  check_every: int = 16):
-        free = isinstance(K, TangentOperator)
-        if not free and not isinstance(K, TangentMatrix):
+        if not isinstance(K, (TangentMatrix, TangentOperator)):
             raise TypeError(f"K must be a TangentMatrix, got {type(K).__name__}")
-        from .multilevel import MultilevelPreconditioner
+        super().__init__(K, preconditioner, rtol, atol, maxiter, check_every)
+        # (the multilevel preconditioner's program holds the solver's kernels too: z and rz come from its cycle)
+        self._code = self._ml._code if self._ml is not None else compile_kernels(K.gdim, self.preconditioner is not None)
 
-        if free and isinstance(preconditioner, str) and preconditioner == "multilevel":
-            raise ValueError('preconditioner="multilevel" builds the multilevel preconditioner of a matrix: with a TangentOperator A pass the instance, '
-                             f"MultilevelPreconditioner(A), or one of {PRECONDITIONERS}")
-        if free and isinstance(preconditioner, MultilevelPreconditioner) and preconditioner.K is not K:
-            raise ValueError("the MultilevelPreconditioner was built for another object: the multilevel preconditioner of a TangentOperator A is "
-                             "MultilevelPreconditioner(A), built on this very operator")
-        if isinstance(preconditioner, str) and preconditioner == "multilevel":
-            pass  # built below, once everything else has been validated
-        elif isinstance(preconditioner, MultilevelPreconditioner):
-            if preconditioner.K is not K:
-                raise ValueError("the MultilevelPreconditioner was built for another matrix")
-        elif not (preconditioner is None or (isinstance(preconditioner, str) and preconditioner == "block_jacobi")):
-            raise ValueError(f"preconditioner must be one of {PRECONDITIONERS + ('multilevel',)} or a MultilevelPreconditioner of K, got {preconditioner!r}")
-        for name, v in (("rtol", rtol), ("atol", atol)):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-                raise TypeError(f"{name} must be a number, got {type(v).__name__}")
-            if not (v >= 0.0 and np.isfinite(v)):
-                raise ValueError(f"{name} must be finite and not negative, got {v}")
-        n = K.shape[0]
-        if maxiter is None:
-            maxiter = 10 * n
-        for name, v, least in (("maxiter", maxiter, 0), ("check_every", check_every, 1)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise TypeError(f"{name} must be an integer, got {type(v).__name__}")
-            if v < least or v >= 2**31:
-                raise ValueError(f"{name} must lie in [{least}, 2^31), got {v}")
-        if free:
-            missing = np.flatnonzero(K.valence == 0)
-            if missing.size:
-                raise ValueError(f"node {int(missing[0])} belongs to no cell: it has no diagonal block, its row is empty, the matrix singular")
-        else:
-            missing = np.flatnonzero(K.diag_block < 0)
-        if missing.size:
-            raise ValueError(f"node {int(missing[0])} has no diagonal block in the pattern: its row is empty, the matrix singular")
-        if isinstance(preconditioner, str) and preconditioner == "multilevel":
-            preconditioner = MultilevelPreconditioner(K)
-        self.K = K
-        self.preconditioner = preconditioner
-        self.rtol, self.atol, self.maxiter, self.check_every = float(rtol), float(atol), int(maxiter), int(check_every)
-        self._op = _operator(K)
-        #: the multilevel preconditioner, whose program holds the solver's kernels too (z and rz come from its cycle), or None
-        self._ml = preconditioner if isinstance(preconditioner, MultilevelPreconditioner) else None
-        self._code = self._ml._code if self._ml is not None else compile_kernels(K.gdim, preconditioner is not None)
-        self.n = n
-        self._work = {}  # device index -> (control, r, z, p, q, inv)
-        self._work_blocks = {}  # device index -> the block array of a TangentOperator's block-Jacobi
-
-    # ---- what the compiler made ------------------------------------------------------------------------------------------------
     @property
     def resources(self) -> dict:
         """``{"vgprs", "sgprs", "scratch_bytes", "lds_bytes", "waves_per_simd", ...}`` of the matrix-vector kernel, under "update",
@@ -496,15 +580,8 @@ class ConjugateGradient:
         r["slab"] = SLAB
         return r
 
-    @property
-    def compile_log(self) -> str:
-        return self._code.log
-
-    @property
-    def device(self) -> int:
-        return self.K.device
-
     def _workspace(self, dev: int):
+        """(control, r, z, p, q, inv)"""
         w = self._work.get(dev)
         if w is None:
             import torch
@@ -517,82 +594,28 @@ class ConjugateGradient:
             w = self._work[dev] = (_Control(dev, self._op.nseg), *vectors, inv)
         return w
 
-    def _diagonal_blocks(self, dev: int):
-        """the block array of a ``TangentOperator``'s block-Jacobi, ``[n_nodes][D][D]``, one per device"""
-        blocks = self._work_blocks.get(dev)
-        if blocks is None:
-            import torch
+    def _start(self, dev: int, values, b, x, has_x0: bool, work):
+        control, r, z, p, q, inv = work
+        op, code, ml, n = self._op, self._code, self._ml, self.n
+        a = op.args(dev, values, control)
+        a.b, a.x, a.r, a.z, a.p, a.q, a.inv = (t.data_ptr() for t in (b, x, r, z, p, q, inv))
+        a.has_x0 = 1 if has_x0 else 0
+        self._inverses(dev, values, a, control)
+        if has_x0:
+            op.apply(code, dev, a, x.data_ptr(), q.data_ptr(), _MODE_PLAIN)
+        a.mode = _MODE_START
+        jit.launch(code, dev, op.blocks(dev), a, "ConjugateGradient start launch", kernel=UPDATE_KERNEL)
+        if ml is not None:
+            ml._cycle(dev, values, control, r.data_ptr(), z.data_ptr())
+            ml._close(dev, control, r, z, p, start=True)
+        direction_blocks = max(1, min(-(-n // 256), BLOCKS_PER_CU * jit.num_cu(dev)))
 
-            blocks = self._work_blocks[dev] = torch.zeros(self.K.gdim**2 * self.K.n_nodes, dtype=torch.float64, device=torch.device("cuda", dev))
-        return blocks
-
-    def __call__(self, values, b, x0=None, out=None) -> SolveResult:
-        """solve ``K x = b`` (synchronous at its end); with a ``TangentOperator`` the first argument is the tangent of the quadrature
-        points: ``cg(tangent, b, x0=None, out=None)``"""
-        import torch
-
-        K, dev, n = self.K, self.device, self.n
-        free = isinstance(K, TangentOperator)  # (values is the tangent of the quadrature points then)
-        if free:
-            K._check("tangent", values, K.tangent_dim * K.n_points, dev)
-        else:
-            K._check("values", values, K.nnz, dev)
-        K._check("b", b, n, dev)
-        if x0 is not None:
-            K._check("x0", x0, n, dev)
-        if out is not None:
-            K._check("out", out, n, dev)
-            if _overlap(out, b):
-                raise ValueError("out must not alias b")
-            if x0 is not None and _overlap(out, x0) and out.data_ptr() != x0.data_ptr():
-                raise ValueError("out may be x0 itself, not a part of it")
-        op = self._op
-        with torch.cuda.device(dev):
-            d = torch.device("cuda", dev)
-            if out is None:
-                x = torch.zeros(n, dtype=torch.float64, device=d) if x0 is None else x0.clone()
-            else:
-                x = out
-                if x0 is None:
-                    x.zero_()
-                elif x.data_ptr() != x0.data_ptr():
-                    x.copy_(x0)
-            if n == 0:
-                return SolveResult(x, 0, True, "converged", 0.0, 0.0, 0)
-            control, r, z, p, q, inv = self._workspace(dev)
-            control.upload(self.rtol, self.atol, self.maxiter)
-            a = op.args(dev, values, control)
-            a.b, a.x, a.r, a.z, a.p, a.q, a.inv = (t.data_ptr() for t in (b, x, r, z, p, q, inv))
-            a.has_x0 = 0 if x0 is None else 1
-            cap = BLOCKS_PER_CU * jit.num_cu(dev)
-            ml = self._ml
-            if free and self.preconditioner and ml is None:  # the nodes' own blocks without a matrix: a BSR values array over the diagonal pattern
-                a.values = K.diagonal_blocks(values, out=self._diagonal_blocks(dev)).data_ptr()
-            if ml is not None:  # (on an operator ``values`` is the tangent: the preconditioner forms the blocks and level 1 from it)
-                ml._setup(dev, values, control)
-            elif self.preconditioner:
-                jit.launch(self._code, dev, max(1, min(-(-K.n_nodes // 256), cap)), a, "ConjugateGradient inverse launch", kernel=INVERSE_KERNEL)
-            if free:
-                a.values = values.data_ptr()
-            if x0 is not None:
-                op.apply(self._code, dev, a, x.data_ptr(), q.data_ptr(), _MODE_PLAIN)
-            a.mode = _MODE_START
-            jit.launch(self._code, dev, op.blocks(dev), a, "ConjugateGradient start launch", kernel=UPDATE_KERNEL)
+        def iterate():
+            op.apply(code, dev, a, p.data_ptr(), q.data_ptr(), _MODE_ITERATE)
+            jit.launch(code, dev, op.blocks(dev), a, "ConjugateGradient update launch", kernel=UPDATE_KERNEL)
             if ml is not None:
                 ml._cycle(dev, values, control, r.data_ptr(), z.data_ptr())
-                ml._close(dev, control, r, z, p, start=True)
-            direction_blocks = max(1, min(-(-n // 256), cap))
-            control.download(dev)  # a solve that ends at its start (b = 0, a singular block, maxiter = 0) enqueues no iteration
-            looks = 1
-            while int(control.ints[_STATUS]) == 0:
-                for _ in range(self.check_every):
-                    op.apply(self._code, dev, a, p.data_ptr(), q.data_ptr(), _MODE_ITERATE)
-                    jit.launch(self._code, dev, op.blocks(dev), a, "ConjugateGradient update launch", kernel=UPDATE_KERNEL)
-                    if ml is not None:
-                        ml._cycle(dev, values, control, r.data_ptr(), z.data_ptr())
-                        ml._close(dev, control, r, z, p, start=False)
-                    jit.launch(self._code, dev, direction_blocks, a, "ConjugateGradient direction launch", kernel=DIRECTION_KERNEL)
-                control.download(dev)
-                looks += 1
-            h, status = control.host, int(control.ints[_STATUS])
-            return SolveResult(x, int(control.ints[_ITERATIONS]), status == 1, STATUSES[status], float(np.sqrt(h[_RR])), float(np.sqrt(h[_BB])), looks)
+                ml._close(dev, control, r, z, p, start=False)
+            jit.launch(code, dev, direction_blocks, a, "ConjugateGradient direction launch", kernel=DIRECTION_KERNEL)
+
+        return iterate
