@@ -35,13 +35,12 @@ whole cells.
 from __future__ import annotations
 
 import ctypes as C
-import re
 
 import numpy as np
 
 from . import gradient, jit
-from .device import _is_torch
-from .gradient import BLOCKS_PER_CU, LDS_CAP, WAVES_LADDER, DisplacementGradient, lds_bytes
+from ._fe_common import BLOCKS_PER_CU, check_tensor, compile_ladder, doubles, kernel_resources, per_device, upload
+from .gradient import LDS_CAP, DisplacementGradient, lds_bytes
 
 ELEMENT_KERNEL = "fcamd_internal_force_element_kernel"
 NODE_KERNEL = "fcamd_internal_force_node_kernel"
@@ -75,15 +74,6 @@ def program(gdim: int, nodes_per_cell: int, points_per_cell: int, affine: bool, 
     return "\n".join(lines) + "\n"
 
 
-def kernel_resources(log: str, kernel: str) -> dict:
-    """``jit.parse_resources`` of the remarks of ONE kernel of a program that holds several"""
-    parts = re.split(r"(?=Function Name: )", log)
-    for part in parts:
-        if part.startswith(f"Function Name: {kernel}"):
-            return jit.parse_resources(part)
-    raise RuntimeError(f"no resource remarks for {kernel} in the compile log")
-
-
 def compile_without_scratch(text: str, name: str, entry: str, kernels):
     """``jit.compile_program(text, name, entry)``; one of ``kernels`` with scratch is a ``ValueError`` that names it"""
     code = jit.compile_program(text, name, entry)
@@ -110,23 +100,12 @@ def compile_kernels(gdim: int, nodes_per_cell: int, points_per_cell: int, affine
         raise ValueError(f"the reference table of {points_per_cell} x {nodes_per_cell} x {gdim} doubles needs {need} bytes of LDS per block "
                          f"with the wave regions; at most {LDS_CAP} fit")
     name = f"internal_force_{gdim}d_{nodes_per_cell}n_{points_per_cell}q_{source}"
-    fallback = None
-    for w in WAVES_LADDER if waves is None else (waves,):
-        code = jit.compile_program(program(gdim, nodes_per_cell, points_per_cell, affine, layout, source, accumulate, w), name, ELEMENT_KERNEL)
-        code.waves = w
-        if waves is not None:
-            return code
-        scratch = [kernel_resources(code.log, k)["scratch_bytes"] for k in (ELEMENT_KERNEL, NODE_KERNEL)]
-        if any(scratch):
-            continue
-        # __launch_bounds__ is a hint: the compiler may take more registers than the budget allows waves for (cells with many
-        # points do); such a budget is not the one the kernel runs at
-        if kernel_resources(code.log, ELEMENT_KERNEL)["vgprs"] <= VGPRS_PER_SIMD // w:
-            return code
-        fallback = fallback or code
-    if fallback is not None:
-        return fallback
-    raise RuntimeError(f"{name}: the kernels use {scratch} bytes of scratch per lane at every register budget")
+    # __launch_bounds__ is a hint: the compiler may take more registers than the budget allows waves for (cells with many points
+    # do); such a budget is not the one the kernel runs at.  Where every budget is overrun, the first without scratch is kept.
+    return compile_ladder(lambda w: program(gdim, nodes_per_cell, points_per_cell, affine, layout, source, accumulate, w), name, ELEMENT_KERNEL, waves,
+                          (ELEMENT_KERNEL, NODE_KERNEL), keep_overrun=True,
+                          accept=lambda log, w: kernel_resources(log, ELEMENT_KERNEL)["vgprs"] <= VGPRS_PER_SIMD // w,
+                          exhausted=lambda s: RuntimeError(f"{name}: the kernels use {s} bytes of scratch per lane at every register budget"))
 
 
 def node_adjacency(dofmap: np.ndarray, n_nodes: int):
@@ -230,32 +209,15 @@ class InternalForce:
         return self.op.device
 
     def _tables(self, dev: int):
-        t = self._on.get(dev)
-        if t is None:
-            import torch
+        t = self._on.get(dev)  # (the hit stays inline: this is on the path of every call)
+        return t if t is not None else per_device(self._on, dev, lambda d: upload(d, self._weights, self.node_ptr, self.adjacency))
 
-            from .hostio import to_device
+    def _element_forces(self, dev: int):
+        """``fe[C][A][D]`` on ``dev``, made at the first use: the one buffer between the element and the node kernel (a caller on the
+        path of every call looks into ``_fe`` first; the operator's product uses the buffer too)"""
+        return per_device(self._fe, dev, lambda d: doubles(self.n_cells * self.nodes_per_cell * self.gdim, d))
 
-            d = torch.device("cuda", dev)
-            with torch.cuda.device(d):
-                t = self._on[dev] = (to_device(self._weights, d), to_device(self.node_ptr, d), to_device(self.adjacency, d))
-        return t
-
-    def _check(self, name: str, a, numel: int, dev: int):
-        import torch
-
-        if not _is_torch(a):
-            raise TypeError(f"{name} must be a torch CUDA tensor, got {type(a).__name__}")
-        if a.dtype != torch.float64:
-            raise TypeError(f"{name} must be float64, got {a.dtype}")
-        if not a.is_cuda or (a.device.index or 0) != dev:
-            raise ValueError(f"{name} is on {a.device}, the operator on cuda:{dev}")
-        if not a.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-        if a.numel() != numel:
-            raise ValueError(f"{name} has {a.numel()} entries, expected {numel}")
-        if a.data_ptr() % 16:
-            raise ValueError(f"{name} must be 16-byte aligned")
+    _check = staticmethod(check_tensor)  # (name, a, numel, dev): the solvers call K._check
 
     def _run(self, source: str, src, grad, out, accumulate: bool):
         import torch
@@ -283,7 +245,7 @@ class InternalForce:
             weights, node_ptr, adj = self._tables(dev)
             fe = self._fe.get(dev)
             if fe is None:
-                fe = self._fe[dev] = torch.empty(self.n_cells * self.nodes_per_cell * self.gdim, dtype=torch.float64, device=torch.device("cuda", dev))
+                fe = self._element_forces(dev)
             cap = BLOCKS_PER_CU * jit.num_cu(dev)
             tiles = -(-self.n_cells // self.cells_per_tile)
             ea = ElementArgs(src.data_ptr(), 0 if grad is None else grad.data_ptr(), ref.data_ptr(), jinv.data_ptr(), weights.data_ptr(),

@@ -29,16 +29,14 @@ import ctypes as C
 import numpy as np
 
 from . import _capi, jit
+from ._fe_common import BLOCKS_PER_CU, WAVES_LADDER, doubles, per_device, upload
 from .device import _check_torch, _is_torch
 
 KERNEL = "fcamd_displacement_gradient_kernel"
 LAYOUTS = ("nabla_grad", "grad")
 #: the most LDS one block may use (bytes): the static limit of a block; two such blocks fit a compute unit's 160 KiB
 LDS_CAP = 64 * 1024
-#: register budgets (waves per SIMD) tried in order; the first that compiles without scratch is kept
-WAVES_LADDER = (8, 4, 2)
-#: blocks per compute unit the grid is capped at (the waves loop over the remaining tiles)
-BLOCKS_PER_CU = 16
+# (WAVES_LADDER, the register budgets tried in order, and BLOCKS_PER_CU, the cap of a grid, are _fe_common's; they are read from here)
 
 
 def lds_bytes(gdim: int, nodes_per_cell: int, points_per_cell: int) -> int:
@@ -71,6 +69,7 @@ def compile_kernel(gdim: int, nodes_per_cell: int, points_per_cell: int, affine:
     name = f"displacement_gradient_{gdim}d_{nodes_per_cell}n_{points_per_cell}q"
     if waves is not None:
         return jit.compile_program(program(gdim, nodes_per_cell, points_per_cell, affine, layout, waves), name, KERNEL)
+    # (one kernel, no register test, no budget noted on the code object: the ladder of _fe_common.compile_ladder does not fit without flags)
     for w in WAVES_LADDER:
         code = jit.compile_program(program(gdim, nodes_per_cell, points_per_cell, affine, layout, w), name, KERNEL)
         if not code.resources.get("scratch_bytes"):
@@ -213,17 +212,8 @@ class DisplacementGradient:
         return self._device
 
     def _tables(self, dev: int):
-        t = self._on.get(dev)
-        if t is None:
-            import torch
-
-            d = torch.device("cuda", dev)
-            from .hostio import to_device
-
-            with torch.cuda.device(d):
-                t = self._on[dev] = (to_device(self._dofmap, d), to_device(self._ref, d), to_device(self._jinv, d),
-                                     torch.empty(self.gdim * self.n_nodes, dtype=torch.float64, device=d))
-        return t
+        t = self._on.get(dev)  # (the hit stays inline: this is on the path of every call)
+        return t if t is not None else per_device(self._on, dev, lambda d: upload(d, self._dofmap, self._ref, self._jinv) + (doubles(self.gdim * self.n_nodes, d),))
 
     def __call__(self, displacement, out=None):
         """``grad_del_u`` of ``displacement`` (ndarray or device tensor of ``D * n_nodes`` float64) as a float64 device tensor of

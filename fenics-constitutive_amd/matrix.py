@@ -30,15 +30,16 @@ import ctypes as C
 import numpy as np
 
 from . import jit
+from ._fe_common import SCRATCH_BYTES  # noqa: F401  (the default of scratch_bytes: read from here)
+from ._fe_common import (ChunkedPass, ConstraintMask, blocks_for, check_tensor, compile_ladder, even, kernel_resources, launch_cap, per_device, upload,
+                         vector_registers)
 from .device import _is_torch
-from .force import MANDEL_DIM, VGPRS_PER_SIMD, InternalForce, kernel_resources
-from .gradient import BLOCKS_PER_CU, LDS_CAP, WAVES_LADDER
+from .force import MANDEL_DIM, VGPRS_PER_SIMD, InternalForce
+from .gradient import LDS_CAP
 
 ELEMENT_KERNEL = "fcamd_tangent_matrix_element_kernel"
 GATHER_KERNEL = "fcamd_tangent_matrix_gather_kernel"
 FORMATS = ("bsr", "csr")
-#: bytes of element matrices between the two kernels unless the caller says otherwise: 256 MiB, 466 033 hexahedra of 576 doubles
-SCRATCH_BYTES = 256 * 1024 * 1024
 #: points of a tile whose inputs sit in a wave's LDS region at a time: the first that fits ``LDS_CAP``
 SLABS = (16, 8, 4, 2, 1)
 
@@ -50,16 +51,12 @@ def cells_per_tile(gdim: int, nodes_per_cell: int) -> int:
     return max(1, 64 // (gdim * nodes_per_cell))
 
 
-def _even(n: int) -> int:
-    return (n + 1) // 2 * 2
-
-
 def lds_bytes(gdim: int, nodes_per_cell: int, points_per_cell: int, affine: bool, slab: int) -> int:
     """LDS of one block of the element kernel: the reference table and four wave regions, each the tangent rows, the per-point
     inverse Jacobians, the basis gradients and the weights of ``slab`` points (every part padded to 16 bytes)"""
     s = MANDEL_DIM[gdim]
-    region = _even(slab * s * s) + (0 if affine else _even(slab * gdim * gdim)) + _even(slab * gdim * nodes_per_cell) + _even(slab)
-    return 8 * (_even(gdim * nodes_per_cell * points_per_cell) + 4 * region)
+    region = even(slab * s * s) + (0 if affine else even(slab * gdim * gdim)) + even(slab * gdim * nodes_per_cell) + even(slab)
+    return 8 * (even(gdim * nodes_per_cell * points_per_cell) + 4 * region)
 
 
 def slab_points(gdim: int, nodes_per_cell: int, points_per_cell: int, affine: bool) -> int:
@@ -89,19 +86,12 @@ def compile_kernels(gdim: int, nodes_per_cell: int, points_per_cell: int, affine
         raise ValueError("a cell needs at least one node and one quadrature point")
     slab = slab_points(gdim, nodes_per_cell, points_per_cell, affine)
     name = f"tangent_matrix_{gdim}d_{nodes_per_cell}n_{points_per_cell}q"
-    scratch = None
-    for w in WAVES_LADDER if waves is None else (waves,):
-        code = jit.compile_program(program(gdim, nodes_per_cell, points_per_cell, affine, slab, w), name, ELEMENT_KERNEL)
-        code.waves, code.slab = w, slab
-        if waves is not None:
-            return code
-        res = kernel_resources(code.log, ELEMENT_KERNEL)
-        scratch = [res["scratch_bytes"], kernel_resources(code.log, GATHER_KERNEL)["scratch_bytes"]]
-        # __launch_bounds__ is a hint: a budget the compiler overran is not the one the kernel runs at
-        if not any(scratch) and res["vgprs"] + (res["agprs"] or 0) <= VGPRS_PER_SIMD // w:
-            return code
-    raise ValueError(f"{name}: the element matrix of {gdim * nodes_per_cell} columns does not compile without scratch at any register budget "
-                     f"(last: {scratch} bytes per lane)")
+    # __launch_bounds__ is a hint: a budget the compiler overran is not the one the kernel runs at
+    return compile_ladder(lambda w: program(gdim, nodes_per_cell, points_per_cell, affine, slab, w), name, ELEMENT_KERNEL, waves,
+                          (ELEMENT_KERNEL, GATHER_KERNEL), slab=slab,
+                          accept=lambda log, w: vector_registers(log, ELEMENT_KERNEL) <= VGPRS_PER_SIMD // w,
+                          exhausted=lambda s: ValueError(f"{name}: the element matrix of {gdim * nodes_per_cell} columns does not compile without scratch at "
+                                                         f"any register budget (last: {s} bytes per lane)"))
 
 
 def block_pattern(dofmap: np.ndarray, n_nodes: int):
@@ -155,7 +145,7 @@ class GatherArgs(C.Structure):
                 ("key_lo", C.c_int64), ("key_hi", C.c_int64), ("cell0", C.c_int64), ("first", C.c_int32), ("accumulate", C.c_int32)]
 
 
-class TangentMatrix:
+class TangentMatrix(ConstraintMask):
     """``K(tangent) -> values``: the tangent stiffness of the mesh of an ``InternalForce`` as a sparse matrix on the GPU.
 
     ``force``: the ``InternalForce`` whose operator (dofmap, reference gradients, inverse Jacobians, device) and weights are
@@ -194,22 +184,17 @@ class TangentMatrix:
                 raise ValueError(f"pattern_dofmap must be [cells][nodes per cell], got shape {pattern_dofmap.shape}")
             if pattern_dofmap.size and (int(pattern_dofmap.min()) < 0 or int(pattern_dofmap.max()) >= n_nodes):
                 raise ValueError(f"pattern_dofmap entries must lie in [0, {n_nodes})")
-        if scratch_bytes is None:
-            scratch_bytes = SCRATCH_BYTES
-        if isinstance(scratch_bytes, bool) or not isinstance(scratch_bytes, (int, np.integer)):
-            raise TypeError(f"scratch_bytes must be an integer, got {type(scratch_bytes).__name__}")
         m = a_ * d_
         cw = cells_per_tile(d_, a_)
-        if scratch_bytes < cw * m * m * 8:
-            raise ValueError(f"scratch_bytes = {scratch_bytes} does not hold one tile of {cw} element matrices of {m} x {m} doubles ({cw * m * m * 8} bytes)")
+        self._pass = ChunkedPass(force, scratch_bytes, m * m * 8, cw, lambda have, tile: f"scratch_bytes = {have} does not hold one tile of {cw} element "
+                                 f"matrices of {m} x {m} doubles ({tile} bytes)")
         self.force, self.op, self.format = force, op, format
         self.gdim, self.nodes_per_cell, self.points_per_cell = d_, a_, q_
         self.n_cells, self.n_points, self.n_nodes = op.n_cells, op.n_points, n_nodes
         self.tangent_dim = MANDEL_DIM[d_] ** 2
         self._code = compile_kernels(d_, a_, q_, op.affine)  # (raises the ValueError of the LDS cap and of the registers)
         self.cells_per_tile = cw
-        self.scratch_bytes = int(scratch_bytes)
-        self.chunk_cells = int(scratch_bytes) // (m * m * 8) // cw * cw  # whole tiles
+        self.scratch_bytes, self.chunk_cells = self._pass.scratch_bytes, self._pass.chunk_cells
         # the symbolic phase
         self.indptr, self.indices = block_pattern(op._dofmap if pattern_dofmap is None else pattern_dofmap, n_nodes)
         self.nnzb = int(self.indices.size)
@@ -237,19 +222,11 @@ class TangentMatrix:
         else:
             self.dest_base, self.dest_stride = csr_base, csr_stride.astype(np.int32)
         # the range of blocks every chunk's cells touch: a later chunk's gather runs over it alone
-        self.chunk_blocks = []
-        if self.n_cells and self.nnzb:
-            block_of = np.empty(self.contributions.size, dtype=np.int32)  # by c*A*A + a*A + b
-            block_of[self.contributions] = np.repeat(np.arange(self.nnzb, dtype=np.int32), np.diff(self.blk_ptr))
-            starts = np.arange(0, self.n_cells, self.chunk_cells, dtype=np.int64) * (a_ * a_)
-            self.chunk_blocks = list(zip(np.minimum.reduceat(block_of, starts).tolist(), (np.maximum.reduceat(block_of, starts) + 1).tolist()))
-            del block_of
+        self.chunk_blocks = self._pass.block_ranges(self.contributions, self.blk_ptr, self.nnzb, a_ * a_)
         # the node's own block (-1: none)
         self.diag_block = np.full(n_nodes, -1, dtype=np.int64)
         on_diagonal = np.flatnonzero(self.indices == self.block_row)
         self.diag_block[self.block_row[on_diagonal]] = on_diagonal
-        self._mask = None
-        self._mask_version = 0
         self._on = {}  # device index -> the pattern tables
         self._scratch = {}  # device index -> element matrices of a chunk
         self._mask_on = {}  # device index -> (version, mask tensor)
@@ -277,74 +254,23 @@ class TangentMatrix:
     def device(self) -> int:
         return self.op.device
 
-    # ---- constraints -----------------------------------------------------------------------------------------------------------
-    def set_constrained(self, mask) -> None:
-        """``mask``: bool ``[D n_nodes]``, true at the Dirichlet dofs, or ``None``.  Uploaded at the next call, and again only when
-        it changes.  A constrained dof whose node has no diagonal block in the pattern is a ``ValueError``"""
-        if mask is None:
-            if self._mask is not None:
-                self._mask, self._mask_version = None, self._mask_version + 1
-            return
-        if not isinstance(mask, np.ndarray):
-            raise TypeError(f"mask must be a numpy.ndarray or None, got {type(mask).__name__}")
-        if mask.dtype != np.bool_:
-            raise TypeError(f"mask must be bool, got {mask.dtype}")
-        if mask.shape != (self.shape[0],):
-            raise ValueError(f"mask must have shape {(self.shape[0],)} (one entry per dof), got {mask.shape}")
-        nodes = np.flatnonzero(mask) // self.gdim
-        missing = nodes[self.diag_block[nodes] < 0]
-        if missing.size:
-            raise ValueError(f"node {int(missing[0])} has a constrained dof and no diagonal block in the pattern: its row cannot be made the identity's")
-        if self._mask is None or not np.array_equal(self._mask, mask):
-            self._mask, self._mask_version = np.ascontiguousarray(mask).copy(), self._mask_version + 1
+    # ---- constraints (set_constrained, _mask_table: ConstraintMask) ---------------------------------------------------------------
+    _no_own_block = "no diagonal block in the pattern: its row cannot be made the identity's"
+
+    def _without_own_block(self, nodes):
+        return self.diag_block[nodes] < 0
 
     # ---- device tables ---------------------------------------------------------------------------------------------------------
     def _tables(self, dev: int):
-        t = self._on.get(dev)
-        if t is None:
-            import torch
+        t = self._on.get(dev)  # (the hit stays inline: this is on the path of every call)
+        return t if t is not None else per_device(self._on, dev, lambda d: upload(d, self.blk_ptr, self.contributions, self.dest_base, self.dest_stride, self.block_row,
+                                                          self.indices))
 
-            from .hostio import to_device
-
-            d = torch.device("cuda", dev)
-            with torch.cuda.device(d):
-                t = self._on[dev] = tuple(to_device(x, d) for x in (self.blk_ptr, self.contributions, self.dest_base, self.dest_stride,
-                                                                    self.block_row, self.indices))
-        return t
-
-    def _mask_table(self, dev: int):
-        if self._mask is None:
-            return None
-        have = self._mask_on.get(dev)
-        if have is None or have[0] != self._mask_version:
-            import torch
-
-            from .hostio import to_device
-
-            d = torch.device("cuda", dev)
-            with torch.cuda.device(d):
-                have = self._mask_on[dev] = (self._mask_version, to_device(self._mask.view(np.uint8), d))
-        return have[1]
-
-    def _check(self, name: str, a, numel: int, dev: int):
-        import torch
-
-        if not _is_torch(a):
-            raise TypeError(f"{name} must be a torch CUDA tensor, got {type(a).__name__}")
-        if a.dtype != torch.float64:
-            raise TypeError(f"{name} must be float64, got {a.dtype}")
-        if not a.is_cuda or (a.device.index or 0) != dev:
-            raise ValueError(f"{name} is on {a.device}, the operator on cuda:{dev}")
-        if not a.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-        if a.numel() != numel:
-            raise ValueError(f"{name} has {a.numel()} entries, expected {numel}")
-        if a.data_ptr() % 16:
-            raise ValueError(f"{name} must be 16-byte aligned")
+    _check = staticmethod(check_tensor)  # (name, a, numel, dev): the solvers call K._check
 
     def chunks(self):
         """the ascending cell ranges ``(first, end)`` a call runs one after the other"""
-        return [(c, min(c + self.chunk_cells, self.n_cells)) for c in range(0, self.n_cells, self.chunk_cells)]
+        return self._pass.chunks()
 
     def __call__(self, tangent, out=None, accumulate: bool = False):
         """the values of ``K`` for this tangent (asynchronous, on torch's current stream)"""
@@ -356,40 +282,31 @@ class TangentMatrix:
         self._check("tangent", tangent, self.tangent_dim * self.n_points, dev)
         if out is not None:
             self._check("out", out, self.nnz, dev)
-        d_, a_, q_ = self.gdim, self.nodes_per_cell, self.points_per_cell
-        m = a_ * d_
+        d_, a_ = self.gdim, self.nodes_per_cell
         with torch.cuda.device(dev):
-            d = torch.device("cuda", dev)
             if out is None:
-                out = torch.empty((self.nnzb, d_, d_) if self.format == "bsr" else (self.nnz,), dtype=torch.float64, device=d)
+                out = torch.empty((self.nnzb, d_, d_) if self.format == "bsr" else (self.nnz,), dtype=torch.float64, device=torch.device("cuda", dev))
             if self.nnz == 0:
                 return out
-            _, ref, jinv, _ = self.op._tables(dev)
-            weights = self.force._tables(dev)[0]
             blk_ptr, contrib, dest_base, dest_stride, block_row, block_col = self._tables(dev)
             mask = self._mask_table(dev)
-            cap = BLOCKS_PER_CU * jit.num_cu(dev)
-            gather_blocks = min((self.nnz + 255) // 256, cap)  # a lane per entry
+            cap = launch_cap(dev)
+            gather_blocks = blocks_for(self.nnz, cap)  # a lane per entry
             ga = GatherArgs(0, blk_ptr.data_ptr(), contrib.data_ptr(), dest_base.data_ptr(), dest_stride.data_ptr(), block_row.data_ptr(),
                             block_col.data_ptr(), 0 if mask is None else mask.data_ptr(), out.data_ptr(), 0, self.nnz, 0, 0, 0, 1,
                             1 if accumulate else 0)
             if self.n_cells == 0:  # no contributions: the entries are started (zeros, out's values, the constrained constants) and left
                 jit.launch(self._code, dev, gather_blocks, ga, "TangentMatrix gather launch", kernel=GATHER_KERNEL)
                 return out
-            ke = self._scratch.get(dev)
-            if ke is None:
-                ke = self._scratch[dev] = torch.empty(min(self.chunk_cells, self.n_cells) * m * m, dtype=torch.float64, device=d)
-            ga.ke = ke.data_ptr()
-            jstride = 8 * d_ * d_ * (1 if self.op.affine else q_)
-            for k, (c0, c1) in enumerate(self.chunks()):
-                ea = ElementArgs(tangent.data_ptr() + 8 * self.tangent_dim * q_ * c0, ref.data_ptr(), jinv.data_ptr() + jstride * c0,
-                                 weights.data_ptr() + 8 * q_ * c0, ke.data_ptr(), c1 - c0)
-                tiles = -(-(c1 - c0) // self.cells_per_tile)
-                jit.launch(self._code, dev, min((tiles + 3) // 4, cap), ea, "TangentMatrix element launch")  # a wave per tile, 4 waves per block
+            ref = self.op._tables(dev)[1].data_ptr()
+            ke = ga.ke = self._pass.buffer(self._scratch, dev).data_ptr()
+            for k, c0, c1, tangent_ptr, jinv_ptr, weights_ptr, element_blocks in self._pass.walk(dev, tangent, cap):
+                ea = ElementArgs(tangent_ptr, ref, jinv_ptr, weights_ptr, ke, c1 - c0)
+                jit.launch(self._code, dev, element_blocks, ea, "TangentMatrix element launch")
                 ga.key_lo, ga.key_hi, ga.cell0, ga.first = c0 * a_ * a_, c1 * a_ * a_, c0, 1 if k == 0 else 0
                 if k:  # the first chunk starts every entry; a later one visits the blocks its cells touch
                     ga.entry0, ga.n_entries = d_ * d_ * self.chunk_blocks[k][0], d_ * d_ * self.chunk_blocks[k][1]
-                    gather_blocks = min((ga.n_entries - ga.entry0 + 255) // 256, cap)
+                    gather_blocks = blocks_for(ga.n_entries - ga.entry0, cap)
                 jit.launch(self._code, dev, gather_blocks, ga, "TangentMatrix gather launch", kernel=GATHER_KERNEL)
         return out
 
@@ -417,19 +334,16 @@ class TangentMatrix:
         dev = self.device
         self._check("values", values, self.nnz, dev)
         d_ = self.gdim
-        t = self._diag_on.get(dev)
-        if t is None:
-            from .hostio import to_device
 
+        def positions(d):
             k = np.maximum(self.diag_block, 0)
             base = self.dest_base[k] if self.nnzb else np.zeros(self.n_nodes, dtype=np.int64)
             stride = self.dest_stride[k].astype(np.int64) if self.nnzb else np.zeros(self.n_nodes, dtype=np.int64)
             pos = base[:, None, None] + stride[:, None, None] * np.arange(d_)[None, :, None] + np.arange(d_)[None, None, :]
             present = np.broadcast_to((self.diag_block >= 0)[:, None, None], pos.shape)
-            with torch.cuda.device(dev):
-                t = self._diag_on[dev] = (to_device(np.where(present, pos, 0), torch.device("cuda", dev)),
-                                          to_device(present.copy(), torch.device("cuda", dev)))
-        pos, present = t
+            return upload(d, np.where(present, pos, 0), present.copy())
+
+        pos, present = per_device(self._diag_on, dev, positions)
         with torch.cuda.device(dev):
             if self.nnz == 0:
                 return torch.zeros((self.n_nodes, d_, d_), dtype=torch.float64, device=torch.device("cuda", dev))

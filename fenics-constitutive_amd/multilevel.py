@@ -104,6 +104,7 @@ import numpy as np
 
 from . import jit, solver
 from . import matrix as _matrix
+from ._fe_common import ChunkedPass, blocks_for
 from .force import compile_without_scratch, kernel_resources
 from .gradient import BLOCKS_PER_CU
 from .matrix import TangentMatrix
@@ -379,10 +380,10 @@ class _FreeFine:
         d_, a_ = A.gdim, A.nodes_per_cell
         m = a_ * d_
         self.cells_per_tile = cw = _matrix.cells_per_tile(d_, a_)
-        if A.scratch_bytes < cw * m * m * 8:
-            raise ValueError(f"the operator's scratch_bytes = {A.scratch_bytes} does not hold one tile of {cw} element matrices of {m} x {m} doubles "
-                             f"({cw * m * m * 8} bytes): the multilevel preconditioner forms its first coarse level from them")
-        self.chunk_cells = A.scratch_bytes // (m * m * 8) // cw * cw  # whole tiles
+        # (the scratch itself is the preconditioner's: ``_OnDevice.ke``, with its other tensors)
+        self._pass = ChunkedPass(A.force, A.scratch_bytes, m * m * 8, cw, lambda have, tile: f"the operator's scratch_bytes = {have} does not hold one tile of "
+                                 f"{cw} element matrices of {m} x {m} doubles ({tile} bytes): the multilevel preconditioner forms its first coarse level from them")
+        self.chunk_cells = self._pass.chunk_cells
         # the pattern of the TangentMatrix of the same force; a node of no cell (that matrix would lack its diagonal block) gets a row of
         # its own block, as a pattern_dofmap with a cell of its own would give it: the block is zero, the status of a setup singular_block
         unused = np.flatnonzero(A.valence == 0).astype(np.int32)
@@ -394,8 +395,7 @@ class _FreeFine:
 
     def chunks(self):
         """the ascending cell ranges ``(first, end)`` whose element matrices pass through the scratch one after the other"""
-        n = self.K.n_cells
-        return [(c, min(c + self.chunk_cells, n)) for c in range(0, n, self.chunk_cells)]
+        return self._pass.chunks()
 
     def build(self, levels: list, rigid: bool = False) -> None:
         """the programs and, with a coarse level, its contribution lists (host); ``rigid``: the gather of multilevel_free_rigid.hip"""
@@ -408,11 +408,8 @@ class _FreeFine:
         fine, coarse = levels[0], levels[1]
         self.blk_ptr, self.contributions = _matrix.contribution_lists(fine.agg[A.op._dofmap], coarse.n_nodes, coarse.indptr, coarse.indices)
         self.block_row = coarse.block_row
-        if A.n_cells and coarse.nnzb:  # the range of coarse blocks every chunk's cells touch: a later chunk's gather runs over it alone
-            block_of = np.empty(self.contributions.size, dtype=np.int32)  # by c*A*A + a*A + b
-            block_of[self.contributions] = np.repeat(np.arange(coarse.nnzb, dtype=np.int32), np.diff(self.blk_ptr))
-            starts = np.arange(0, A.n_cells, self.chunk_cells, dtype=np.int64) * (a_ * a_)
-            self.chunk_blocks = list(zip(np.minimum.reduceat(block_of, starts).tolist(), (np.maximum.reduceat(block_of, starts) + 1).tolist()))
+        # the range of coarse blocks every chunk's cells touch: a later chunk's gather runs over it alone
+        self.chunk_blocks = self._pass.block_ranges(self.contributions, self.blk_ptr, coarse.nnzb, a_ * a_)
 
     def product(self, pc, dev: int, tangent, control, x_ptr: int, q_ptr: int, cap: int) -> list:
         # (quiet mode neither reads nor writes the control block: a product enqueued behind the end of a solve writes the
@@ -431,11 +428,9 @@ class _FreeFine:
         import torch
 
         A, on = self.K, pc._device(dev)
-        d_, a_, q_ = A.gdim, A.nodes_per_cell, A.points_per_cell
-        m = a_ * d_
+        d_, a_ = A.gdim, A.nodes_per_cell
         dd = d_ * d_
-        dofmap, ref, jinv, _ = A.op._tables(dev)
-        weights = A.force._tables(dev)[0]
+        dofmap, ref, _, _ = A.op._tables(dev)
         mask = A._mask_table(dev)
         t0, t1 = on.tables[0], on.tables[1]
         common = (on.ke.data_ptr(), t1["blk_ptr"].data_ptr(), t1["contrib"].data_ptr(), dofmap.data_ptr(), 0 if mask is None else mask.data_ptr(),
@@ -456,13 +451,10 @@ class _FreeFine:
             return pc._blocks(lanes * (hi - lo), cap)
 
         gather_blocks = cover(0, pc._levels[1].nnzb)
-        jstride = 8 * dd * (1 if A.op.affine else q_)
         with torch.cuda.device(dev):
-            for k, (c0, c1) in enumerate(self.chunks()):
-                ea = _matrix.ElementArgs(tangent.data_ptr() + 8 * A.tangent_dim * q_ * c0, ref.data_ptr(), jinv.data_ptr() + jstride * c0,
-                                         weights.data_ptr() + 8 * q_ * c0, on.ke.data_ptr(), c1 - c0)
-                tiles = -(-(c1 - c0) // self.cells_per_tile)
-                jit.launch(self.element_code, dev, min((tiles + 3) // 4, cap), ea, "MultilevelPreconditioner element launch")  # a wave per tile, 4 waves per block
+            for k, c0, c1, tangent_ptr, jinv_ptr, weights_ptr, element_blocks in self._pass.walk(dev, tangent, cap):
+                ea = _matrix.ElementArgs(tangent_ptr, ref.data_ptr(), jinv_ptr, weights_ptr, on.ke.data_ptr(), c1 - c0)
+                jit.launch(self.element_code, dev, element_blocks, ea, "MultilevelPreconditioner element launch")
                 ga.key_lo, ga.key_hi, ga.cell0, ga.first = c0 * a_ * a_, c1 * a_ * a_, c0, 1 if k == 0 else 0
                 if k:  # the first chunk starts every entry; a later one visits the coarse blocks its cells touch
                     gather_blocks = cover(*self.chunk_blocks[k])
@@ -741,7 +733,7 @@ class MultilevelPreconditioner:
 
     @staticmethod
     def _blocks(n: int, cap: int) -> int:
-        return max(1, min(-(-n // 256), cap))
+        return max(1, blocks_for(n, cap))  # a lane per entry, never an empty grid
 
     def _setup(self, dev: int, values, control) -> None:
         """the Galerkin values of every coarse level, then the inverses of every level's own blocks (asynchronous)"""

@@ -75,6 +75,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import jit
+from ._fe_common import overlap, per_device, upload
 from .force import compile_without_scratch, kernel_resources
 from .gradient import BLOCKS_PER_CU, LDS_CAP
 from .matrix import TangentMatrix
@@ -208,16 +209,8 @@ class _Seam:
         self.matrix._check(self.first, values, self.first_numel, dev)
 
     def tables(self, dev: int):
-        t = self._on.get(dev)
-        if t is None:
-            import torch
-
-            from .hostio import to_device
-
-            d = torch.device("cuda", dev)
-            with torch.cuda.device(d):
-                t = self._on[dev] = tuple(to_device(x, d) for x in self._host_tables())
-        return t
+        t = self._on.get(dev)  # (the hit stays inline: this is on the path of every call)
+        return t if t is not None else per_device(self._on, dev, lambda d: upload(d, *self._host_tables()))
 
     def control(self, dev: int) -> _Control:
         c = self._control.get(dev)
@@ -413,9 +406,7 @@ def dot(a, b) -> float:
     return float(control.host[_DOT])
 
 
-def _overlap(a, b) -> bool:
-    a0, b0 = a.data_ptr(), b.data_ptr()
-    return a0 < b0 + 8 * b.numel() and b0 < a0 + 8 * a.numel()
+_overlap = overlap  # (bicgstab_free.py and multilevel.py read it from here)
 
 
 class _Krylov:

@@ -39,9 +39,10 @@ import ctypes as C
 import numpy as np
 
 from . import jit
-from .force import MANDEL_DIM, MAX_POINTS_PER_CELL, VGPRS_PER_SIMD, InternalForce, cells_per_tile, kernel_resources
-from .gradient import BLOCKS_PER_CU, LDS_CAP, WAVES_LADDER, lds_bytes
-from .matrix import SCRATCH_BYTES
+from ._fe_common import (ChunkedPass, ConstraintMask, blocks_for, check_tensor, compile_ladder, even, kernel_resources, launch_cap, overlap, tile_blocks,
+                         vector_registers)
+from .force import MANDEL_DIM, MAX_POINTS_PER_CELL, VGPRS_PER_SIMD, InternalForce, cells_per_tile
+from .gradient import LDS_CAP, lds_bytes
 
 ELEMENT_KERNEL = "fcamd_tangent_operator_element_kernel"
 NODE_KERNEL = "fcamd_tangent_operator_node_kernel"
@@ -63,17 +64,13 @@ def diagonal_cells_per_tile(nodes_per_cell: int) -> int:
     return max(1, 64 // nodes_per_cell)
 
 
-def _even(n: int) -> int:
-    return (n + 1) // 2 * 2
-
-
 def diagonal_slab(gdim: int, nodes_per_cell: int, affine: bool) -> int:
     """points of a slab of the diagonal-block kernel: the most (up to ``MAX_SLAB``) whose tangent rows, per-point inverse Jacobians,
     basis gradients and weights fit a wave's region of ``64 * D*D`` doubles, every part padded to 16 bytes (``ValueError`` where not
     even one point does)"""
     s = MANDEL_DIM[gdim]
     for slab in range(MAX_SLAB, 0, -1):
-        need = _even(slab * s * s) + (0 if affine else _even(slab * gdim * gdim)) + _even(slab * gdim * nodes_per_cell) + _even(slab)
+        need = even(slab * s * s) + (0 if affine else even(slab * gdim * gdim)) + even(slab * gdim * nodes_per_cell) + even(slab)
         if need <= 64 * gdim * gdim:
             return slab
     raise ValueError(f"the basis gradients of {nodes_per_cell} nodes x {gdim} at one point do not fit the wave's region of {64 * gdim * gdim} doubles "
@@ -105,18 +102,10 @@ def compile_kernels(gdim: int, nodes_per_cell: int, points_per_cell: int, affine
                          f"with the wave regions; at most {LDS_CAP} fit")
     slab = diagonal_slab(gdim, nodes_per_cell, affine)
     name = f"tangent_operator_{gdim}d_{nodes_per_cell}n_{points_per_cell}q"
-    scratch = None
-    for w in WAVES_LADDER if waves is None else (waves,):
-        code = jit.compile_program(program(gdim, nodes_per_cell, points_per_cell, affine, slab, w), name, ELEMENT_KERNEL)
-        code.waves, code.slab = w, slab
-        if waves is not None:
-            return code
-        scratch = [kernel_resources(code.log, k)["scratch_bytes"] for k in KERNELS]
-        res = kernel_resources(code.log, ELEMENT_KERNEL)
-        # __launch_bounds__ is a hint: a budget the compiler overran is not the one the kernel runs at
-        if not any(scratch) and res["vgprs"] + (res["agprs"] or 0) <= VGPRS_PER_SIMD // w:
-            return code
-    raise ValueError(f"{name}: the kernels do not compile without scratch at any register budget (last: {scratch} bytes per lane)")
+    # __launch_bounds__ is a hint: a budget the compiler overran is not the one the kernel runs at
+    return compile_ladder(lambda w: program(gdim, nodes_per_cell, points_per_cell, affine, slab, w), name, ELEMENT_KERNEL, waves, KERNELS, slab=slab,
+                          accept=lambda log, w: vector_registers(log, ELEMENT_KERNEL) <= VGPRS_PER_SIMD // w,
+                          exhausted=lambda s: ValueError(f"{name}: the kernels do not compile without scratch at any register budget (last: {s} bytes per lane)"))
 
 
 class ElementArgs(C.Structure):
@@ -146,7 +135,7 @@ class DiagNodeArgs(C.Structure):
                [("n_entries", C.c_int64), ("key_lo", C.c_int64), ("key_hi", C.c_int64), ("first", C.c_int32), ("pad", C.c_int32)]
 
 
-class TangentOperator:
+class TangentOperator(ConstraintMask):
     """``A(tangent, v) -> y`` and ``A.diagonal_blocks(tangent)``: the tangent stiffness of the mesh of an ``InternalForce`` applied
     without a matrix, on the GPU.
 
@@ -170,16 +159,11 @@ class TangentOperator:
     def __init__(self, force: InternalForce, scratch_bytes: int | None = None):
         if not isinstance(force, InternalForce):
             raise TypeError(f"force must be an InternalForce, got {type(force).__name__}")
-        if scratch_bytes is None:
-            scratch_bytes = SCRATCH_BYTES
-        if isinstance(scratch_bytes, bool) or not isinstance(scratch_bytes, (int, np.integer)):
-            raise TypeError(f"scratch_bytes must be an integer, got {type(scratch_bytes).__name__}")
         op = force.op
         d_, a_, q_ = op.gdim, op.nodes_per_cell, op.points_per_cell
         cw = diagonal_cells_per_tile(a_)
-        if scratch_bytes < cw * a_ * d_ * d_ * 8:
-            raise ValueError(f"scratch_bytes = {scratch_bytes} does not hold one tile of {cw} cells' diagonal blocks of {a_} x {d_} x {d_} doubles "
-                             f"({cw * a_ * d_ * d_ * 8} bytes)")
+        self._pass = ChunkedPass(force, scratch_bytes, a_ * d_ * d_ * 8, cw, lambda have, tile: f"scratch_bytes = {have} does not hold one tile of {cw} cells' "
+                                 f"diagonal blocks of {a_} x {d_} x {d_} doubles ({tile} bytes)")
         rows = np.sort(op._dofmap, axis=1)
         twice = np.flatnonzero((rows[:, 1:] == rows[:, :-1]).any(axis=1))
         if twice.size:
@@ -190,13 +174,10 @@ class TangentOperator:
         self.n_cells, self.n_points, self.n_nodes = op.n_cells, op.n_points, op.n_nodes
         self.tangent_dim = MANDEL_DIM[d_] ** 2
         self.shape = (d_ * op.n_nodes, d_ * op.n_nodes)
-        self.scratch_bytes = int(scratch_bytes)
+        self.scratch_bytes, self.chunk_cells = self._pass.scratch_bytes, self._pass.chunk_cells
         self.diagonal_cells_per_tile = cw
-        self.chunk_cells = int(scratch_bytes) // (a_ * d_ * d_ * 8) // cw * cw  # whole tiles
         #: cells of every node: a node of none has an empty row
         self.valence = np.diff(force.node_ptr.astype(np.int64))
-        self._mask = None
-        self._mask_version = 0
         self._mask_on = {}  # device index -> (version, mask tensor)
         self._scratch = {}  # device index -> the diagonal blocks of a chunk's cells
 
@@ -224,43 +205,13 @@ class TangentOperator:
     def device(self) -> int:
         return self.op.device
 
-    # ---- constraints -----------------------------------------------------------------------------------------------------------
-    def set_constrained(self, mask) -> None:
-        """``mask``: bool ``[D n_nodes]``, true at the Dirichlet dofs, or ``None``.  Uploaded at the next call, and again only when
-        it changes.  A constrained dof whose node belongs to no cell is a ``ValueError``, as it is for ``TangentMatrix``"""
-        if mask is None:
-            if self._mask is not None:
-                self._mask, self._mask_version = None, self._mask_version + 1
-            return
-        if not isinstance(mask, np.ndarray):
-            raise TypeError(f"mask must be a numpy.ndarray or None, got {type(mask).__name__}")
-        if mask.dtype != np.bool_:
-            raise TypeError(f"mask must be bool, got {mask.dtype}")
-        if mask.shape != (self.shape[0],):
-            raise ValueError(f"mask must have shape {(self.shape[0],)} (one entry per dof), got {mask.shape}")
-        nodes = np.flatnonzero(mask) // self.gdim
-        missing = nodes[self.valence[nodes] == 0]
-        if missing.size:
-            raise ValueError(f"node {int(missing[0])} has a constrained dof and belongs to no cell: it has no diagonal block to make the identity's")
-        if self._mask is None or not np.array_equal(self._mask, mask):
-            self._mask, self._mask_version = np.ascontiguousarray(mask).copy(), self._mask_version + 1
+    # ---- constraints (set_constrained, _mask_table: ConstraintMask; the refusal is the one of ``TangentMatrix``) ------------------
+    _no_own_block = "belongs to no cell: it has no diagonal block to make the identity's"
 
-    def _mask_table(self, dev: int):
-        if self._mask is None:
-            return None
-        have = self._mask_on.get(dev)
-        if have is None or have[0] != self._mask_version:
-            import torch
+    def _without_own_block(self, nodes):
+        return self.valence[nodes] == 0
 
-            from .hostio import to_device
-
-            d = torch.device("cuda", dev)
-            with torch.cuda.device(d):
-                have = self._mask_on[dev] = (self._mask_version, to_device(self._mask.view(np.uint8), d))
-        return have[1]
-
-    def _check(self, name: str, a, numel: int, dev: int):
-        self.force._check(name, a, numel, dev)
+    _check = staticmethod(check_tensor)  # (name, a, numel, dev): the solvers call K._check
 
     # ---- the product -----------------------------------------------------------------------------------------------------------
     def _apply(self, dev: int, tangent_ptr: int, v_ptr: int, out_ptr: int, mode: int, partials_ptr: int = 0, control_ptr: int = 0) -> None:
@@ -273,27 +224,23 @@ class TangentOperator:
     def _launches(self, dev: int, tangent_ptr: int, v_ptr: int, out_ptr: int, mode: int, partials_ptr: int = 0, control_ptr: int = 0) -> list:
         """the launches of ``_apply`` as ``[(code, kernel, blocks, args, what)]``, for a caller that keeps them (the launch plan of the
         multilevel preconditioner): they hold the pointers given here, those of ``force``'s tables and element forces and the mask's"""
-        import torch
-
         force, op = self.force, self.op
         nd = self.shape[0]
         _, node_ptr, adj = force._tables(dev)
         mask = self._mask_table(dev)
         mask_ptr = 0 if mask is None else mask.data_ptr()
-        cap = BLOCKS_PER_CU * jit.num_cu(dev)
+        cap = launch_cap(dev)
         fe_ptr = 0
         ops = []
         if self.n_cells:
             dofmap, ref, jinv, _ = op._tables(dev)
             weights = force._tables(dev)[0]
             fe = force._fe.get(dev)
-            if fe is None:
-                fe = force._fe[dev] = torch.empty(self.n_cells * self.nodes_per_cell * self.gdim, dtype=torch.float64, device=torch.device("cuda", dev))
-            fe_ptr = fe.data_ptr()
+            fe_ptr = (fe if fe is not None else force._element_forces(dev)).data_ptr()
             tiles = -(-self.n_cells // cells_per_tile(self.gdim, self.points_per_cell))
             ea = ElementArgs(tangent_ptr, v_ptr, dofmap.data_ptr(), mask_ptr, ref.data_ptr(), jinv.data_ptr(), weights.data_ptr(), fe_ptr,
                              control_ptr, self.n_cells, mode, 0)
-            ops.append((self._code, None, min((tiles + 3) // 4, cap), ea, "TangentOperator element launch"))  # a wave per tile, 4 waves per block
+            ops.append((self._code, None, tile_blocks(tiles, cap), ea, "TangentOperator element launch"))
         nseg = -(-nd // SEG)
         na = NodeArgs(fe_ptr, node_ptr.data_ptr(), adj.data_ptr(), v_ptr, mask_ptr, out_ptr, partials_ptr, control_ptr, nd, nseg, mode, 0)
         ops.append((self._code, NODE_KERNEL, max(1, min(nseg, cap)), na, "TangentOperator node launch"))  # a block per segment
@@ -309,7 +256,7 @@ class TangentOperator:
         self._check("v", v, nd, dev)
         if out is not None:
             self._check("out", out, nd, dev)
-            if _overlap(out, v):
+            if overlap(out, v):
                 raise ValueError("out must not alias v")
         with torch.cuda.device(dev):
             if out is None:
@@ -320,7 +267,7 @@ class TangentOperator:
     # ---- the diagonal blocks ---------------------------------------------------------------------------------------------------
     def chunks(self):
         """the ascending cell ranges ``(first, end)`` ``diagonal_blocks`` runs one after the other"""
-        return [(c, min(c + self.chunk_cells, self.n_cells)) for c in range(0, self.n_cells, self.chunk_cells)]
+        return self._pass.chunks()
 
     def diagonal_blocks(self, tangent, out=None):
         """device tensor ``[n_nodes][D][D]``: every node's own block of the constrained ``K`` (zeros at a node of no cell) --
@@ -328,42 +275,28 @@ class TangentOperator:
         import torch
 
         dev = self.device
-        d_, a_, q_ = self.gdim, self.nodes_per_cell, self.points_per_cell
+        d_, a_ = self.gdim, self.nodes_per_cell
         dd = d_ * d_
         self._check("tangent", tangent, self.tangent_dim * self.n_points, dev)
         if out is not None:
             self._check("out", out, dd * self.n_nodes, dev)
         with torch.cuda.device(dev):
-            d = torch.device("cuda", dev)
             if out is None:
-                out = torch.empty((self.n_nodes, d_, d_), dtype=torch.float64, device=d)
+                out = torch.empty((self.n_nodes, d_, d_), dtype=torch.float64, device=torch.device("cuda", dev))
             _, node_ptr, adj = self.force._tables(dev)
             mask = self._mask_table(dev)
-            cap = BLOCKS_PER_CU * jit.num_cu(dev)
+            cap = launch_cap(dev)
             na = DiagNodeArgs(0, node_ptr.data_ptr(), adj.data_ptr(), 0 if mask is None else mask.data_ptr(), out.data_ptr(), dd * self.n_nodes,
                               0, 0, 1, 0)
-            node_blocks = max(1, min((dd * self.n_nodes + 255) // 256, cap))  # a lane per entry
+            node_blocks = max(1, blocks_for(dd * self.n_nodes, cap))  # a lane per entry
             if self.n_cells == 0:  # no contributions: the entries are started and left
                 jit.launch(self._code, dev, node_blocks, na, "TangentOperator diagonal node launch", kernel=DIAGONAL_NODE_KERNEL)
                 return out
-            _, ref, jinv, _ = self.op._tables(dev)
-            weights = self.force._tables(dev)[0]
-            de = self._scratch.get(dev)
-            if de is None:
-                de = self._scratch[dev] = torch.empty(min(self.chunk_cells, self.n_cells) * a_ * dd, dtype=torch.float64, device=d)
-            na.de = de.data_ptr()
-            jstride = 8 * dd * (1 if self.op.affine else q_)
-            for k, (c0, c1) in enumerate(self.chunks()):
-                ea = DiagElementArgs(tangent.data_ptr() + 8 * self.tangent_dim * q_ * c0, ref.data_ptr(), jinv.data_ptr() + jstride * c0,
-                                     weights.data_ptr() + 8 * q_ * c0, de.data_ptr(), c1 - c0)
-                tiles = -(-(c1 - c0) // self.diagonal_cells_per_tile)
-                jit.launch(self._code, dev, min((tiles + 3) // 4, cap), ea, "TangentOperator diagonal element launch",
-                           kernel=DIAGONAL_ELEMENT_KERNEL)  # a wave per tile, 4 waves per block
+            ref = self.op._tables(dev)[1].data_ptr()
+            de = na.de = self._pass.buffer(self._scratch, dev).data_ptr()
+            for k, c0, c1, tangent_ptr, jinv_ptr, weights_ptr, element_blocks in self._pass.walk(dev, tangent, cap):
+                ea = DiagElementArgs(tangent_ptr, ref, jinv_ptr, weights_ptr, de, c1 - c0)
+                jit.launch(self._code, dev, element_blocks, ea, "TangentOperator diagonal element launch", kernel=DIAGONAL_ELEMENT_KERNEL)
                 na.key_lo, na.key_hi, na.first = c0 * a_, c1 * a_, 1 if k == 0 else 0
                 jit.launch(self._code, dev, node_blocks, na, "TangentOperator diagonal node launch", kernel=DIAGONAL_NODE_KERNEL)
         return out
-
-
-def _overlap(a, b) -> bool:
-    a0, b0 = a.data_ptr(), b.data_ptr()
-    return a0 < b0 + 8 * b.numel() and b0 < a0 + 8 * a.numel()
