@@ -26,6 +26,8 @@ from fenics_constitutive_amd import tangent_operator as to  # noqa: E402
 from fenics_constitutive_amd.hostio import to_device, to_host  # noqa: E402
 from bicgstab_free_util import K_CYCLES, K_ITERATIONS, K_SHAPES, k_iterations_system, operator_solve  # noqa: E402
 from bicgstab_util import nonassociated_tangent  # noqa: E402
+from fe_gpu_util import CANARY, MARGIN, bits, guarded, assert_margins_intact, assert_same_bits, solve_guarded, assert_same_result, tables_of  # noqa: E402
+from fe_gpu_util import one_cu  # noqa: E402, F401 (the fixture: pytest finds it in this namespace)
 from force_util import MANDEL_DIM, random_inputs  # noqa: E402
 from gradient_util import cube_operator_tables  # noqa: E402
 from multilevel_free_util import FreeOracle  # noqa: E402
@@ -33,8 +35,6 @@ from solver_util import SEG, ordered_dot, spd_tangent  # noqa: E402
 from tangent_operator_util import TILING_SHAPES, distinct_inputs, product_oracle  # noqa: E402
 from tangent_operator_util import operator_solve as cg_operator_solve  # noqa: E402
 
-MARGIN = 64  # doubles on either side of an output (a multiple of two: the output stays on the 16-byte grid)
-CANARY = np.uint64(0x7FF8DEADBEEF0BAD)  # a NaN no arithmetic produces
 TO_SHAPES = ("hex8", "tet_p2", "tri_p2", "interval")
 CYCLES = K_CYCLES
 KINDS = (None, "block_jacobi") + CYCLES
@@ -43,69 +43,12 @@ ITERATING = (to.ELEMENT_KERNEL, bicgstab_free.NODE_DOTS_KERNEL, bicgstab.HALF_KE
              bicgstab.DIRECTION_KERNEL)
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def guarded(nout):
-    """(buffer, view of nout doubles) with canary margins; the view canaries too"""
-    h = np.full(nout + 2 * MARGIN, CANARY, dtype=np.uint64).view(np.float64)
-    buf = to_device(h, "cuda")
-    return buf, buf[MARGIN: MARGIN + nout]
-
-
-def assert_margins_intact(buf, nout):
-    h = bits(to_host(buf))
-    assert (h[:MARGIN] == CANARY).all() and (h[MARGIN + nout:] == CANARY).all(), "a kernel wrote outside its output"
-
-
-def assert_same_bits(have, want, what):
-    diff = bits(have).reshape(-1) != bits(want).reshape(-1)
-    assert not diff.any(), f"{what}: {int(diff.sum())} of {diff.size} entries differ, first at {int(np.argmax(diff))}"
-
-
 def same_number(have, want):
     return bits(np.float64(have)) == bits(np.float64(want))
 
 
-def tables_of(t):
-    return t["dofmap"], t["ref"], t["jinv"], t["weights"], t["n_nodes"]
-
-
 def operator_of(t):
     return fc.TangentOperator(fc.InternalForce(fc.DisplacementGradient(t["dofmap"], t["ref"], t["jinv"], t["n_nodes"]), t["weights"]))
-
-
-@pytest.fixture
-def one_cu(monkeypatch):
-    """the launches capped at the blocks of ONE compute unit (``num_cu`` is looked up on jit at launch); yields (kernel, blocks)"""
-    launches = []
-    real = jit.launch
-
-    def launch(code, device, nblocks, args, what, kernel=None):
-        launches.append((kernel or code.kernel, nblocks))
-        return real(code, device, nblocks, args, what, kernel=kernel)
-
-    monkeypatch.setattr(jit, "num_cu", lambda dev: 1)
-    monkeypatch.setattr(jit, "launch", launch)
-    return launches
-
-
-def solve_guarded(s, tangent, b, x0=None):
-    n = b.size
-    buf, out = guarded(n)
-    tangent = tangent if torch.is_tensor(tangent) else to_device(tangent, "cuda")
-    res = s(tangent, to_device(b, "cuda"), x0=None if x0 is None else to_device(x0, "cuda"), out=out)
-    assert res.x.data_ptr() == out.data_ptr()
-    assert_margins_intact(buf, n)
-    return res, to_host(out)
-
-
-def assert_same_result(res, x, want, what):
-    assert_same_bits(x, want.x, what)
-    assert (res.iterations, res.status, res.converged) == (want.iterations, want.status, want.converged), what
-    assert same_number(res.residual_norm, want.residual_norm), what
-    assert same_number(res.rhs_norm, want.rhs_norm), what
 
 
 def preconditioners(a, tables, kind, mask, **options):

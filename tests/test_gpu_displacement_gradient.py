@@ -24,28 +24,13 @@ from fenics_constitutive_amd.hostio import to_device, to_host  # noqa: E402
 from fenics_constitutive_amd.integration import use_resident_problem_state, use_resident_state  # noqa: E402
 from fenics_constitutive_amd.problem import ResidentProblemState  # noqa: E402
 from fenics_constitutive_amd.resident import ResidentState  # noqa: E402
+from fe_gpu_util import CANARY, MARGIN, bits, guarded, assert_margins_intact  # noqa: E402
+from fe_gpu_util import one_cu  # noqa: E402, F401 (the fixture: pytest finds it in this namespace)
 from gradient_util import LAYOUTS, SHAPES, cell_counts, cube_operator_tables, oracle, random_tables, rounding_bound  # noqa: E402
 from test_gpu_integration import Fn, Problem  # noqa: E402
 from test_gpu_parity import make_law, random_case  # noqa: E402
 
 FULL = fc.StressStrainConstraint.FULL
-MARGIN = 64  # doubles on either side of an output (a multiple of two: the output stays on the 16-byte grid)
-CANARY = np.uint64(0x7FF8DEADBEEF0BAD)  # a NaN no arithmetic produces
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def guarded(nout):
-    """(buffer, view of nout doubles) with canary margins"""
-    buf = to_device(np.full(nout + 2 * MARGIN, CANARY, dtype=np.uint64).view(np.float64), "cuda")
-    return buf, buf[MARGIN: MARGIN + nout]
-
-
-def assert_margins_intact(buf, nout):
-    h = bits(to_host(buf))
-    assert (h[:MARGIN] == CANARY).all() and (h[MARGIN + nout:] == CANARY).all(), "the kernel wrote outside its output"
 
 
 def run_and_compare(shape, n_cells, layout, affine, integer, seed):
@@ -81,21 +66,6 @@ def test_bits_of_the_ordered_oracle(shape, layout, affine):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # 2. the grid-stride loop
 # ---------------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture
-def one_cu(monkeypatch):
-    """the launch capped at the blocks of ONE compute unit (gradient.py looks ``num_cu`` up on jit at launch); yields the block counts"""
-    blocks = []
-    real = jit.launch
-
-    def launch(code, device, nblocks, args, what):
-        blocks.append(nblocks)
-        return real(code, device, nblocks, args, what)
-
-    monkeypatch.setattr(jit, "num_cu", lambda dev: 1)
-    monkeypatch.setattr(jit, "launch", launch)
-    return blocks
-
-
 @pytest.mark.parametrize("shape,affine", [("hex8", False), ("q5", True), ("q5", False), ("tri_p2", True), ("tet_p1", True)])
 def test_grid_stride_loop(shape, affine, one_cu):
     q = SHAPES[shape][2]
@@ -106,7 +76,7 @@ def test_grid_stride_loop(shape, affine, one_cu):
     assert (n_cells * q) % 64 != 0 and (n_cells * q) // 64 == 2 * gradient.BLOCKS_PER_CU * 4 + 5
     for integer in (True, False):
         run_and_compare(shape, n_cells, "nabla_grad", affine, integer, seed=3)
-    assert one_cu and all(b == gradient.BLOCKS_PER_CU for b in one_cu), one_cu  # the launches really were capped
+    assert one_cu and all(nb == gradient.BLOCKS_PER_CU for _, nb in one_cu), one_cu  # the launches really were capped
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

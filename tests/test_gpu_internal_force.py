@@ -20,11 +20,11 @@ from fenics_constitutive_amd import force as force_module  # noqa: E402
 from fenics_constitutive_amd import gradient, jit  # noqa: E402
 from fenics_constitutive_amd.hostio import to_device, to_host  # noqa: E402
 from fenics_constitutive_amd.resident import ResidentState  # noqa: E402
+from fe_gpu_util import CANARY, MARGIN, bits, guarded, assert_margins_intact  # noqa: E402
+from fe_gpu_util import one_cu  # noqa: E402, F401 (the fixture: pytest finds it in this namespace)
 from force_util import MANDEL_DIM, OracleLoop, cell_counts, force_oracle, random_inputs, tangent_action_oracle  # noqa: E402
 from gradient_util import SHAPES, cube_operator_tables, oracle  # noqa: E402
 
-MARGIN = 64  # doubles on either side of an output (a multiple of two: the output stays on the 16-byte grid)
-CANARY = np.uint64(0x7FF8DEADBEEF0BAD)  # a NaN no arithmetic produces
 #: gradient_util's shapes, one whose cells per tile the odd rule lowers (64 // 3 = 21 cells would be 567 doubles of jinv: 20), and
 #: two with ONE cell per tile and Q and D odd: no tile base stays on the 16-byte grid and the kernel takes its guarded 8-byte loads
 ALL_SHAPES = dict(SHAPES, q3=(3, 4, 3, True), odd33_1d=(1, 2, 33, False), odd33_3d=(3, 4, 33, False))
@@ -32,24 +32,7 @@ SOURCES = ("stress", "tangent")
 VM_P = {"p_ka": 175000.0, "p_mu": 80769.0, "p_y0": 1200.0, "p_y00": 2500.0, "p_w": 200.0}
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def guarded(nout, fill=None):
-    """(buffer, view of nout doubles) with canary margins; the view canaries too, or ``fill``"""
-    h = np.full(nout + 2 * MARGIN, CANARY, dtype=np.uint64).view(np.float64)
-    if fill is not None:
-        h[MARGIN: MARGIN + nout] = fill
-    buf = to_device(h, "cuda")
-    return buf, buf[MARGIN: MARGIN + nout]
-
-
-def assert_margins_intact(buf, nout):
-    h = bits(to_host(buf))
-    assert (h[:MARGIN] == CANARY).all() and (h[MARGIN + nout:] == CANARY).all(), "a kernel wrote outside its output"
-
-
+# stays here: fe_gpu_util's flattens both sides first, this one compares them in their shapes and so refuses (4,) against (2, 2)
 def assert_same_bits(have, want, what):
     diff = bits(have) != bits(want)
     assert not diff.any(), f"{what}: {int(diff.sum())} of {diff.size} entries differ, first at {int(np.argmax(diff))}"
@@ -120,21 +103,6 @@ def test_bits_of_the_ordered_oracle(shape, source, affine):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # 2. the grid-stride loops of both kernels
 # ---------------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture
-def one_cu(monkeypatch):
-    """the launches capped at the blocks of ONE compute unit (force.py looks ``num_cu`` up on jit at launch); yields (kernel, blocks)"""
-    launches = []
-    real = jit.launch
-
-    def launch(code, device, nblocks, args, what, kernel=None):
-        launches.append((kernel or code.kernel, nblocks))
-        return real(code, device, nblocks, args, what, kernel=kernel)
-
-    monkeypatch.setattr(jit, "num_cu", lambda dev: 1)
-    monkeypatch.setattr(jit, "launch", launch)
-    return launches
-
-
 @pytest.mark.parametrize("source", SOURCES)
 @pytest.mark.parametrize("shape,affine", [("hex8", False), ("q5", True), ("q3", False), ("tri_p2", True)])
 def test_grid_stride_loops(shape, affine, source, one_cu):

@@ -17,79 +17,27 @@ torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
 import fe_mini as FE  # noqa: E402
-from cube_tension_device_solve import tension_constraints, tension_test_device_solve  # noqa: E402
-from cube_tension_matrix_free import cube_operators  # noqa: E402
+from cube_tension_device_solve import tension_test_device_solve  # noqa: E402
 from cube_tension_matrix_free_multilevel import matrix_free_multilevel_loop  # noqa: E402
 
 import fenics_constitutive_amd as fc  # noqa: E402
 from fenics_constitutive_amd import gradient, jit, matrix, multilevel, solver  # noqa: E402
 from fenics_constitutive_amd import tangent_operator as to  # noqa: E402
 from fenics_constitutive_amd.hostio import to_device, to_host  # noqa: E402
+from fe_gpu_util import CANARY, MARGIN, bits, guarded, assert_margins_intact, assert_same_bits, solve_guarded, assert_same_result  # noqa: E402
+from fe_gpu_util import tables_of, force_of, status_of, cube_system_of  # noqa: E402
+from fe_gpu_util import one_cu  # noqa: E402, F401 (the fixture: pytest finds it in this namespace)
 from force_util import MANDEL_DIM, cell_counts  # noqa: E402
-from gradient_util import cube_operator_tables  # noqa: E402
 import multilevel_free_util as MF  # noqa: E402
 import multilevel_util as MU  # noqa: E402
 from solver_util import SEG, from_format, spd_tangent  # noqa: E402
 from tangent_operator_util import TILING_SHAPES as SHAPES  # noqa: E402
 from tangent_operator_util import distinct_inputs, operator_solve, random_mask  # noqa: E402
 
-MARGIN = 64  # doubles on either side of an output (a multiple of two: the output stays on the 16-byte grid)
-CANARY = np.uint64(0x7FF8DEADBEEF0BAD)  # a NaN no arithmetic produces
 ML_SHAPES = ("hex8", "tet_p2", "tri_p2", "interval")
 CYCLES = ("multiplicative", "additive")
 VM_P = {"p_ka": 175000.0, "p_mu": 80769.0, "p_y0": 1200.0, "p_y00": 2500.0, "p_w": 200.0}
 SINGULAR = solver.STATUSES.index("singular_block")
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def guarded(nout):
-    """(buffer, view of nout doubles) with canary margins; the view canaries too"""
-    h = np.full(nout + 2 * MARGIN, CANARY, dtype=np.uint64).view(np.float64)
-    buf = to_device(h, "cuda")
-    return buf, buf[MARGIN: MARGIN + nout]
-
-
-def assert_margins_intact(buf, nout):
-    h = bits(to_host(buf))
-    assert (h[:MARGIN] == CANARY).all() and (h[MARGIN + nout:] == CANARY).all(), "a kernel wrote outside its output"
-
-
-def assert_same_bits(have, want, what):
-    diff = bits(have).reshape(-1) != bits(want).reshape(-1)
-    assert not diff.any(), f"{what}: {int(diff.sum())} of {diff.size} entries differ, first at {int(np.argmax(diff))}"
-
-
-def tables_of(t):
-    return t["dofmap"], t["ref"], t["jinv"], t["weights"], t["n_nodes"]
-
-
-def force_of(t):
-    return fc.InternalForce(fc.DisplacementGradient(t["dofmap"], t["ref"], t["jinv"], t["n_nodes"]), t["weights"])
-
-
-@pytest.fixture
-def one_cu(monkeypatch):
-    """the launches capped at the blocks of ONE compute unit (``num_cu`` is looked up on jit at launch); yields (kernel, blocks)"""
-    launches = []
-    real = jit.launch
-
-    def launch(code, device, nblocks, args, what, kernel=None):
-        launches.append((kernel or code.kernel, nblocks))
-        return real(code, device, nblocks, args, what, kernel=kernel)
-
-    monkeypatch.setattr(jit, "num_cu", lambda dev: 1)
-    monkeypatch.setattr(jit, "launch", launch)
-    return launches
-
-
-def status_of(pc):
-    """the status the preconditioner's own control block holds behind setup() or apply()"""
-    control = pc._on[pc.device].control
-    control.download(pc.device)
-    return int(control.ints[solver._STATUS])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -137,16 +85,6 @@ def test_setup_on_the_bits(shape, affine):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # 2. one application
 # ---------------------------------------------------------------------------------------------------------------------------------
-def cube_system_of(mesh, seed, scratch_bytes=None):
-    op, f = cube_operators(mesh)
-    dofmap, ref, jinv = cube_operator_tables(mesh)
-    tables = (dofmap, ref, jinv, f._weights, mesh.n_nodes)
-    mask, _ = tension_constraints(mesh)
-    a = fc.TangentOperator(f, scratch_bytes=scratch_bytes)
-    a.set_constrained(mask)
-    return f, tables, mask, a, spd_tangent(mesh.n_points, 6, seed, False)
-
-
 @pytest.fixture(scope="module")
 def small_cube():
     """the tension-test operator of Cube(5, 4, 3) (120 nodes) on a random positive definite tangent; the scratch holds 16 of the 60
@@ -211,22 +149,6 @@ def big_cube():
     oracles = {CYCLES[0]: first, CYCLES[1]: copy.copy(first)}  # (the values and inverses do not depend on the cycle: formed once)
     oracles[CYCLES[1]].cycle = CYCLES[1]
     return mesh, tables, mask, a, tangent, oracles
-
-
-def solve_guarded(cg, tangent, b, x0=None):
-    n = b.size
-    buf, out = guarded(n)
-    res = cg(tangent if torch.is_tensor(tangent) else to_device(tangent, "cuda"), to_device(b, "cuda"), x0=None if x0 is None else to_device(x0, "cuda"), out=out)
-    assert res.x.data_ptr() == out.data_ptr()
-    assert_margins_intact(buf, n)
-    return res, to_host(out)
-
-
-def assert_same_result(res, x, want, what):
-    assert_same_bits(x, want.x, what)
-    assert (res.iterations, res.status, res.converged) == (want.iterations, want.status, want.converged), what
-    assert bits(np.float64(res.residual_norm)) == bits(np.float64(want.residual_norm)), what
-    assert bits(np.float64(res.rhs_norm)) == bits(np.float64(want.rhs_norm)), what
 
 
 @pytest.mark.parametrize("cycle", CYCLES)

@@ -25,69 +25,18 @@ import fenics_constitutive_amd as fc  # noqa: E402
 from fenics_constitutive_amd import gradient, jit, multilevel, solver  # noqa: E402
 from fenics_constitutive_amd.hostio import to_device, to_host  # noqa: E402
 from bicgstab_util import bicgstab as oracle_bicgstab  # noqa: E402
+from fe_gpu_util import bits, guarded, assert_margins_intact, assert_same_bits, solve_guarded, assert_same_result  # noqa: E402
+from fe_gpu_util import one_cu  # noqa: E402, F401 (the fixture: pytest finds it in this namespace)
 from force_util import MANDEL_DIM, random_inputs  # noqa: E402
 from gradient_util import SHAPES  # noqa: E402
 import multilevel_util as MU  # noqa: E402
 import rigid_body_util as RU  # noqa: E402
 from solver_util import SEG, from_format, spd_tangent  # noqa: E402
 
-MARGIN = 64  # doubles on either side of an output (a multiple of two: the output stays on the 16-byte grid)
-CANARY = np.uint64(0x7FF8DEADBEEF0BAD)  # a NaN no arithmetic produces
 FORMATS = ("bsr", "csr")
 RIGID_SHAPES = ("hex8", "tet_p2", "tri_p2")
 CYCLES = ("multiplicative", "additive")
 SINGULAR = solver.STATUSES.index("singular_block")
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def guarded(nout):
-    """(buffer, view of nout doubles) with canary margins; the view canaries too"""
-    buf = to_device(np.full(nout + 2 * MARGIN, CANARY, dtype=np.uint64).view(np.float64), "cuda")
-    return buf, buf[MARGIN: MARGIN + nout]
-
-
-def assert_margins_intact(buf, nout):
-    h = bits(to_host(buf))
-    assert (h[:MARGIN] == CANARY).all() and (h[MARGIN + nout:] == CANARY).all(), "a kernel wrote outside its output"
-
-
-def assert_same_bits(have, want, what):
-    diff = bits(have).reshape(-1) != bits(want).reshape(-1)
-    assert not diff.any(), f"{what}: {int(diff.sum())} of {diff.size} entries differ, first at {int(np.argmax(diff))}"
-
-
-def solve_guarded(s, values, b, x0=None):
-    n = b.size
-    buf, out = guarded(n)
-    res = s(values, to_device(b, "cuda"), x0=None if x0 is None else to_device(x0, "cuda"), out=out)
-    assert res.x.data_ptr() == out.data_ptr()
-    assert_margins_intact(buf, n)
-    return res, to_host(out)
-
-
-def assert_same_result(res, x, want, what):
-    assert_same_bits(x, want.x, what)
-    assert (res.iterations, res.status, res.converged) == (want.iterations, want.status, want.converged), what
-    assert bits(np.float64(res.residual_norm)) == bits(np.float64(want.residual_norm)), what
-    assert bits(np.float64(res.rhs_norm)) == bits(np.float64(want.rhs_norm)), what
-
-
-@pytest.fixture
-def one_cu(monkeypatch):
-    """the launches capped at the blocks of ONE compute unit; yields (kernel, blocks)"""
-    launches = []
-    real = jit.launch
-
-    def launch(code, device, nblocks, args, what, kernel=None):
-        launches.append((kernel or code.kernel, nblocks))
-        return real(code, device, nblocks, args, what, kernel=kernel)
-
-    monkeypatch.setattr(jit, "num_cu", lambda dev: 1)
-    monkeypatch.setattr(jit, "launch", launch)
-    return launches
 
 
 def assembled(shape, n_cells, seed, fmt, symmetric=False, fraction=0.2):

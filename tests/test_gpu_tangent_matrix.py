@@ -22,38 +22,15 @@ from fenics_constitutive_amd import gradient, jit  # noqa: E402
 from fenics_constitutive_amd import matrix as matrix_module  # noqa: E402
 from fenics_constitutive_amd.hostio import to_device, to_host  # noqa: E402
 from fenics_constitutive_amd.resident import ResidentState  # noqa: E402
+from fe_gpu_util import CANARY, MARGIN, bits, guarded, assert_margins_intact, assert_same_bits  # noqa: E402
+from fe_gpu_util import one_cu  # noqa: E402, F401 (the fixture: pytest finds it in this namespace)
 from force_util import chain_length, random_inputs  # noqa: E402
 from gradient_util import EPS, SHAPES, cube_operator_tables  # noqa: E402
 from matrix_util import (csr_values, diagonal_blocks, matrix_oracle, max_contributions, oracle_matrix_loop, to_bsr)  # noqa: E402
 
-MARGIN = 64  # doubles on either side of an output (a multiple of two: the output stays on the 16-byte grid)
-CANARY = np.uint64(0x7FF8DEADBEEF0BAD)  # a NaN no arithmetic produces
 #: gradient_util's shapes, the odd ones of the force operator's tests and one with more than 64 columns (66: two passes)
 ALL_SHAPES = dict({k: v[:3] for k, v in SHAPES.items()}, q3=(3, 4, 3), odd33_1d=(1, 2, 33), odd33_3d=(3, 4, 33), wide=(3, 22, 2))
 VM_P = {"p_ka": 175000.0, "p_mu": 80769.0, "p_y0": 1200.0, "p_y00": 2500.0, "p_w": 200.0}
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def guarded(nout, fill=None):
-    """(buffer, view of nout doubles) with canary margins; the view canaries too, or ``fill``"""
-    h = np.full(nout + 2 * MARGIN, CANARY, dtype=np.uint64).view(np.float64)
-    if fill is not None:
-        h[MARGIN: MARGIN + nout] = fill
-    buf = to_device(h, "cuda")
-    return buf, buf[MARGIN: MARGIN + nout]
-
-
-def assert_margins_intact(buf, nout):
-    h = bits(to_host(buf))
-    assert (h[:MARGIN] == CANARY).all() and (h[MARGIN + nout:] == CANARY).all(), "a kernel wrote outside its output"
-
-
-def assert_same_bits(have, want, what):
-    diff = bits(have).reshape(-1) != bits(want).reshape(-1)
-    assert not diff.any(), f"{what}: {int(diff.sum())} of {diff.size} entries differ, first at {int(np.argmax(diff))}"
 
 
 def inputs(shape, n_cells, seed, integer, affine):
@@ -142,21 +119,6 @@ def test_bits_of_the_ordered_oracle(shape, affine):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # 2. the grid-stride loops of both kernels
 # ---------------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture
-def one_cu(monkeypatch):
-    """the launches capped at the blocks of ONE compute unit (matrix.py looks ``num_cu`` up on jit at launch); yields (kernel, blocks)"""
-    launches = []
-    real = jit.launch
-
-    def launch(code, device, nblocks, args, what, kernel=None):
-        launches.append((kernel or code.kernel, nblocks))
-        return real(code, device, nblocks, args, what, kernel=kernel)
-
-    monkeypatch.setattr(jit, "num_cu", lambda dev: 1)
-    monkeypatch.setattr(jit, "launch", launch)
-    return launches
-
-
 @pytest.mark.parametrize("shape,affine", [("hex8", False), ("q5", True), ("tet_p2", True), ("tri_p2", False)])
 def test_grid_stride_loops(shape, affine, one_cu):
     d_, a_, q = ALL_SHAPES[shape]

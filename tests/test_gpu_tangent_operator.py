@@ -27,14 +27,14 @@ from fenics_constitutive_amd import gradient, jit, solver  # noqa: E402
 from fenics_constitutive_amd import tangent_operator as to  # noqa: E402
 from fenics_constitutive_amd.hostio import to_device, to_host  # noqa: E402
 from fenics_constitutive_amd.resident import ResidentState  # noqa: E402
+from fe_gpu_util import CANARY, MARGIN, bits, guarded, assert_margins_intact, assert_same_bits, solve_guarded, assert_same_result, tables_of  # noqa: E402
+from fe_gpu_util import one_cu  # noqa: E402, F401 (the fixture: pytest finds it in this namespace)
 from force_util import MANDEL_DIM, cell_counts  # noqa: E402
 from gradient_util import cube_operator_tables  # noqa: E402
 from solver_util import SEG, conjugate_gradient, ordered_dot, spd_tangent  # noqa: E402
 from tangent_operator_util import (NO_MATRIX, TILING_SHAPES, diagonal_blocks_oracle, distinct_inputs, operator_solve, product_oracle,  # noqa: E402
                                    random_mask, tiling_constants)
 
-MARGIN = 64  # doubles on either side of an output (a multiple of two: the output stays on the 16-byte grid)
-CANARY = np.uint64(0x7FF8DEADBEEF0BAD)  # a NaN no arithmetic produces
 TO_SHAPES = ("hex8", "tet_p2", "tri_p2", "interval")
 SHAPES = TILING_SHAPES  # every tiling the template generates (tangent_operator_util.py; test_tangent_operator.py: each branch is reached)
 PRODUCT_SHAPES = tuple(name for name in TILING_SHAPES if name != "wide130")
@@ -42,49 +42,9 @@ SOLVE_SHAPES = TO_SHAPES + ("q3", "odd33_3d", "wide70")
 VM_P = {"p_ka": 175000.0, "p_mu": 80769.0, "p_y0": 1200.0, "p_y00": 2500.0, "p_w": 200.0}
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def guarded(nout):
-    """(buffer, view of nout doubles) with canary margins; the view canaries too"""
-    h = np.full(nout + 2 * MARGIN, CANARY, dtype=np.uint64).view(np.float64)
-    buf = to_device(h, "cuda")
-    return buf, buf[MARGIN: MARGIN + nout]
-
-
-def assert_margins_intact(buf, nout):
-    h = bits(to_host(buf))
-    assert (h[:MARGIN] == CANARY).all() and (h[MARGIN + nout:] == CANARY).all(), "a kernel wrote outside its output"
-
-
-def assert_same_bits(have, want, what):
-    diff = bits(have).reshape(-1) != bits(want).reshape(-1)
-    assert not diff.any(), f"{what}: {int(diff.sum())} of {diff.size} entries differ, first at {int(np.argmax(diff))}"
-
-
-def tables_of(t):
-    return t["dofmap"], t["ref"], t["jinv"], t["weights"], t["n_nodes"]
-
-
 def operators(t, layout="nabla_grad"):
     op = fc.DisplacementGradient(t["dofmap"], t["ref"], t["jinv"], t["n_nodes"], layout=layout)
     return op, fc.InternalForce(op, t["weights"])
-
-
-@pytest.fixture
-def one_cu(monkeypatch):
-    """the launches capped at the blocks of ONE compute unit (``num_cu`` is looked up on jit at launch); yields (kernel, blocks)"""
-    launches = []
-    real = jit.launch
-
-    def launch(code, device, nblocks, args, what, kernel=None):
-        launches.append((kernel or code.kernel, nblocks))
-        return real(code, device, nblocks, args, what, kernel=kernel)
-
-    monkeypatch.setattr(jit, "num_cu", lambda dev: 1)
-    monkeypatch.setattr(jit, "launch", launch)
-    return launches
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -293,22 +253,6 @@ def test_diagonal_blocks_on_one_compute_unit(one_cu):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # 4. solves
 # ---------------------------------------------------------------------------------------------------------------------------------
-def solve_guarded(cg, tangent, b, x0=None):
-    n = b.size
-    buf, out = guarded(n)
-    res = cg(to_device(tangent, "cuda"), to_device(b, "cuda"), x0=None if x0 is None else to_device(x0, "cuda"), out=out)
-    assert res.x.data_ptr() == out.data_ptr()
-    assert_margins_intact(buf, n)
-    return res, to_host(out)
-
-
-def assert_same_result(res, x, want, what):
-    assert_same_bits(x, want.x, what)
-    assert (res.iterations, res.status, res.converged) == (want.iterations, want.status, want.converged), what
-    assert bits(np.float64(res.residual_norm)) == bits(np.float64(want.residual_norm)), what
-    assert bits(np.float64(res.rhs_norm)) == bits(np.float64(want.rhs_norm)), what
-
-
 @pytest.mark.parametrize("shape", SOLVE_SHAPES)
 def test_exactly_k_iterations(shape):
     d_, a_, q_, affine = SHAPES[shape]

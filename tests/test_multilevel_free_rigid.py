@@ -21,6 +21,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import fe_mini as FE  # noqa: E402
 from cube_tension_device_solve import tension_constraints, tension_test_device_solve  # noqa: E402
 from cube_tension_matrix_free import cube_operators  # noqa: E402
+from fe_gpu_util import bits, tables_of  # noqa: E402
 from gradient_util import SHAPES, cube_operator_tables  # noqa: E402
 from matrix_util import matrix_oracle  # noqa: E402
 import multilevel_free_rigid_util as FR  # noqa: E402
@@ -35,14 +36,6 @@ RIGID_SHAPES = tuple(name for name in sorted(SHAPES) if SHAPES[name][0] > 1)  # 
 ORACLE_SHAPES = ("hex8", "tet_p2", "tri_p2")
 VM_P = {"p_ka": 175000.0, "p_mu": 80769.0, "p_y0": 1200.0, "p_y00": 2500.0, "p_w": 200.0}
 KERNEL = "fcamd_mfr_galerkin_kernel"  # multilevel.FREE_RIGID_GALERKIN_KERNEL
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def tables_of(t):
-    return t["dofmap"], t["ref"], t["jinv"], t["weights"], t["n_nodes"]
 
 
 def operator(shape="tet_p2", n_cells=9, seed=3, affine=True, every_node=True, **kwargs):

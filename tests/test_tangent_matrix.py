@@ -14,16 +14,13 @@ from fenics_constitutive_amd import gradient, jit, matrix
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "examples"))
 import fe_mini  # noqa: E402
+from fe_gpu_util import bits  # noqa: E402
 from force_util import chain_length, random_inputs, tangent_action_oracle  # noqa: E402
 from gradient_util import EPS, SHAPES, cube_operator_tables, oracle  # noqa: E402
 from matrix_util import (apply_constraints, contributions, csr_values, matrix_oracle, max_contributions, pattern, to_bsr)  # noqa: E402
 
 #: gradient_util's shapes, the odd ones of the force operator's tests and one with more than 64 columns (66: two passes)
 ALL_SHAPES = dict({k: v[:3] for k, v in SHAPES.items()}, q3=(3, 4, 3), odd33_1d=(1, 2, 33), odd33_3d=(3, 4, 33), wide=(3, 22, 2))
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
 
 
 def operators(shape, n_cells=3, affine=True, seed=0, **kwargs):

@@ -21,6 +21,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import fe_mini as FE  # noqa: E402
 from cube_tension_device_solve import tension_test_device_solve  # noqa: E402
 from fenics_constitutive_amd import force as force_module  # noqa: E402
+from fe_gpu_util import bits  # noqa: E402
 from force_util import chain_length, max_valence, random_inputs  # noqa: E402
 from gradient_util import EPS, SHAPES, cube_operator_tables  # noqa: E402
 from matrix_util import diagonal_blocks, matrix_oracle, to_bsr  # noqa: E402
@@ -29,10 +30,6 @@ from tangent_operator_util import (NO_MATRIX, TILING_SHAPES, dense_diagonal_bloc
 
 VM_P = {"p_ka": 175000.0, "p_mu": 80769.0, "p_y0": 1200.0, "p_y00": 2500.0, "p_w": 200.0}
 ORACLE_SHAPES = ("hex8", "tet_p2", "tri_p2", "interval")
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
 
 
 def operator(shape="tet_p2", n_cells=5, seed=3, every_node=False, **kwargs):
